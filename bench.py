@@ -9,6 +9,16 @@ Metric (BASELINE.json): masked SNVs imputed/s (2 * sum(mask) per sample-window),
 with kNN queries/s reported beside it.  Workload = configs[2] of BASELINE.json:
 window 1024 sites, k = 32, 1M-haplotype panel resident in HBM, d384/L12/H12.
 
+A plain run sets up, warms up, times the K steps and prints the result line; its per-kernel
+figures (``roofline``, ``kernels``) come from the HIP events the library records around each
+launch inside the timed steps (at most the first 64 of them), as they always have, so
+``ms_per_step`` means the same with and without ``--full``.  ``--full`` adds the legs that
+take runs of their own: the kNN search alone and its HBM probes, the C2 embedding-space
+cross-check, the exact-f32 precision leg, the training leg and the CPU baseline.
+``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy (float32;
+the large hidden states as a fixed seeded sample of rows); model, panel, queries and masks
+are seeded, so two builds can be compared output for output.
+
 Launch: python bench.py --gpus N --steps K --warmup W.  N>1 runs one rank per GPU: under
 torch.distributed.run (WORLD_SIZE set) this process is one rank and checks WORLD_SIZE == N;
 started directly, it first checks that N devices are visible (exit 2 otherwise) and then
@@ -46,8 +56,14 @@ def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=None,
                    help="ranks = GPUs (default: WORLD_SIZE under a launcher, else 1)")
-    p.add_argument("--steps", type=int, default=5)
+    p.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the legs that take runs of their own: the kNN search and "
+                        "HBM probes, the C2 cross-check, the exact-f32 precision leg, the training leg and the CPU "
+                        "baseline (each still switched by its own option below)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32")
     p.add_argument("--batch", type=int, default=256,
                    help="samples per step per GPU (configs[4]'s inference batch; 512 haplotype sequences)")
     p.add_argument("--n-ref", type=int, default=1_000_000, help="panel haplotypes")
@@ -74,7 +90,10 @@ def parse(argv=None):
     p.add_argument("--one-device-rehearsal", action="store_true",
                    help="N>1 rehearsal on a one-GPU box: every rank on cuda:0 over gloo (host-staged "
                         "collectives); the numbers are not a measurement")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def _free_port() -> int:
@@ -262,7 +281,6 @@ def main(argv=None):
     model = build_model(len(vocab), args.dims, args.layers, args.heads).to(dev).eval()
     eng = engine_for(model)
     eng.set_dtype(dtype)
-    P = eng.packed()
 
     # ---- window, panel (HBM-resident, generated on device), queries ----
     shard = None
@@ -271,7 +289,7 @@ def main(argv=None):
         shard = PanelShard.current()
     wl = build_workload(args, dev, vocab, rank, shard=shard)
     S, B, L = wl.S, wl.B, wl.L
-    index, x, tok, site_mask = wl.index, wl.x, wl.tok, wl.site_mask
+    index, x = wl.index, wl.x
     af_np, ref_af, raw_mask = wl.af_np, wl.ref_af, wl.raw_mask
     masked_per_step = wl.masked_per_step
     index_sites_pad = index.n_sites_pad
@@ -286,8 +304,13 @@ def main(argv=None):
     lib.snvrag_evlog_enable(cap)
     barrier(world)
     torch.cuda.synchronize()
+    # the event log holds ``cap`` launches: whole steps only, so the per-step figures below
+    # stay per step however many steps are timed
+    log_steps = min(args.steps, 64)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if i == log_steps:
+            lib.snvrag_evlog_pause(1)
         out = step()
     torch.cuda.synchronize()
     barrier(world)
@@ -298,42 +321,15 @@ def main(argv=None):
     n = lib.snvrag_evlog_read(kinds.ctypes.data, ms.ctypes.data, work.ctypes.data, cap)
     lib.snvrag_evlog_enable(0)
     kinds, ms, work = kinds[:n], ms[:n], work[:n]
-    # the whole kNN search (LUT + pre-pass + scan + merges + decode) alone, outside the timed region
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    search = make_search(wl, eng, k)
-    ev0.record()
-    for _ in range(5):
-        search()
-    ev1.record()
-    torch.cuda.synchronize()
-    knn_ms = ev0.elapsed_time(ev1) / 5
-    # HBM-regime probes (SURVEY.md §8d states the HBM target at Bq in {48, 96}): the scan
-    # streams the panel once per launch; up to ~150 queries the int8 MFMA work per code
-    # byte is below the HBM ridge
-    probes = []
-    for nq in (48, 96, 128):
-        tq = tok[:nq].contiguous()
-        index.search(tq, P.W, site_mask, k)
-        lib.snvrag_evlog_enable(cap)
-        for _ in range(5):
-            index.search(tq, P.W, site_mask, k)
-        torch.cuda.synchronize()
-        kk, mm, ww = np.zeros(cap, np.int32), np.zeros(cap, np.float32), np.zeros(cap, np.float64)
-        n2 = lib.snvrag_evlog_read(kk.ctypes.data, mm.ctypes.data, ww.ctypes.data, cap)
-        lib.snvrag_evlog_enable(0)
-        kk, mm, ww = kk[:n2], mm[:n2], ww[:n2]
-        sel = (kk == 4) & (ww >= 0.5 * ww[kk == 4].max())
-        pr = dict(queries=nq, avg_launch_ms=round(float(mm[sel].mean()), 4),
-                  bytes_per_launch=float(ww[sel].mean()),
-                  achieved_gbs=round(float(ww[sel].sum() / (mm[sel].sum() * 1e-3)) / 1e9, 1))
-        pr["frac"] = round(pr["achieved_gbs"] / HBM_PEAK_GBS, 4)
-        probes.append(pr)
-    probe = dict(probes[-1], per_queries=[{kq: p[kq] for kq in ("queries", "avg_launch_ms", "achieved_gbs", "frac")}
-                                          for p in probes])
-    c2 = knn_c2(args, wl, eng, k) if (args.c2_n > 0 and rank == 0 and dtype == torch.bfloat16) else None
-    # precision leg: the same batch through the exact-f32 path, whose logits
-    # carry the 1e-3 parity bar; report how often the bf16 run's imputed calls agree with it
-    precision = precision_leg(args, wl, eng, k, out) if (args.f32_leg and dtype == torch.bfloat16) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+    knn_ms = probe = c2 = precision = None
+    if args.full:
+        knn_ms, probe = knn_probes(wl, eng, k, cap)
+        c2 = knn_c2(args, wl, eng, k) if (args.c2_n > 0 and rank == 0 and dtype == torch.bfloat16) else None
+        # precision leg: the same batch through the exact-f32 path, whose logits
+        # carry the 1e-3 parity bar; report how often the bf16 run's imputed calls agree with it
+        precision = precision_leg(args, wl, eng, k, out) if (args.f32_leg and dtype == torch.bfloat16) else None
     elapsed = max_over_ranks(elapsed, world, dev)
 
     def agg(kind):
@@ -341,8 +337,8 @@ def main(argv=None):
         cnt = int(sel.sum())
         if cnt == 0:
             return None
-        return dict(launches_per_step=cnt / args.steps, avg_ms=float(ms[sel].mean()),
-                    work_per_launch=float(work[sel].mean()), total_ms_per_step=float(ms[sel].sum()) / args.steps,
+        return dict(launches_per_step=cnt / log_steps, avg_ms=float(ms[sel].mean()),
+                    work_per_launch=float(work[sel].mean()), total_ms_per_step=float(ms[sel].sum()) / log_steps,
                     rate=float(work[sel].sum() / (ms[sel].sum() * 1e-3)))
 
     gemm, attn, ln, ffn = agg(1), agg(2), agg(3), agg(8)
@@ -356,7 +352,7 @@ def main(argv=None):
     knn_qps = 2 * B * world * args.steps / elapsed
     del index, out
     torch.cuda.empty_cache()
-    train = train_bench(args, world, rank, dev) if args.train_steps > 0 else None
+    train = train_bench(args, world, rank, dev) if (args.full and args.train_steps > 0) else None
     if rank != 0:
         if world > 1:
             import torch.distributed as dist
@@ -388,11 +384,6 @@ def main(argv=None):
                              prepass_ms=round(prescan["total_ms_per_step"], 4) if prescan else 0.0,
                              note="all queries in one pass over the panel (XCD co-scheduled query groups); "
                                   "above ~150 queries the scan is int8-MFMA/LDS bound, see knn_hbm_probe"),
-            "knn_hbm_probe": dict(probe, bound="hbm", peak=HBM_PEAK_GBS),
-            "knn_c2_embedding_space": c2,
-            "knn_search_ms": round(knn_ms, 4),
-            # (sharded panel: the search serves every rank's queries in that time)
-            "knn_search_queries_per_s": round(2 * B * (world if shard is not None else 1) / (knn_ms * 1e-3), 1),
             "gemm": dict(achieved_tflops=round(gemm["rate"] / 1e12, 2), frac=round(gemm["rate"] / 1e12 / peak_f, 4),
                          ms_per_step=round(gemm["total_ms_per_step"], 3), launches_per_step=gemm["launches_per_step"]),
             "ffn_fused": (dict(achieved_tflops=round(ffn["rate"] / 1e12, 2), frac=round(ffn["rate"] / 1e12 / peak_f, 4),
@@ -405,9 +396,19 @@ def main(argv=None):
         "masked_snvs_per_step_per_gpu": masked_per_step,
     }
     from src.dataset import utils as U
-    cpu = None
-    if args.cpu_baseline and world == 1:             # rank 0 at N = 1 only (the other ranks would idle)
-        cpu = cpu_baseline(args, model, vocab, af_np, ref_af, raw_mask, x, dev)
+    legs = {}
+    if args.full:
+        extra["kernels"].update({
+            "knn_hbm_probe": dict(probe, bound="hbm", peak=HBM_PEAK_GBS),
+            "knn_c2_embedding_space": c2,
+            "knn_search_ms": round(knn_ms, 4),
+            # (sharded panel: the search serves every rank's queries in that time)
+            "knn_search_queries_per_s": round(2 * B * (world if shard is not None else 1) / (knn_ms * 1e-3), 1),
+        })
+        cpu = None
+        if args.cpu_baseline and world == 1:         # rank 0 at N = 1 only (the other ranks would idle)
+            cpu = cpu_baseline(args, model, vocab, af_np, ref_af, raw_mask, x, dev)
+        legs = {"cpu_baseline": cpu, "precision_parity": precision, "train": train}
     line = {
         "metric": "masked SNVs imputed/sec (+ kNN queries/sec), window=1024 k=32",
         "value": round(value, 1), "unit": "masked SNVs/s", "n_gpus": world, "steps": args.steps,
@@ -419,13 +420,81 @@ def main(argv=None):
                    "masked_site_fraction": round(float(raw_mask.mean()), 4),
                    "global_batch": B * world, "seq_len": L, "parallelism": (f"dp{world} + panel sharded {world}-way" if shard is not None
                                                   else f"dp{world} (panel replicated)")},
-        "roofline": roofline, "cpu_baseline": cpu, **extra, "precision_parity": precision, "train": train,
+        "roofline": roofline, **extra, "full": args.full, **legs,
         "distributed": dist_info(world),
     }
     print(json.dumps(line), flush=True)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
+
+
+DUMP_FULL_BYTES = 8 << 20     # an output up to this size (as float32) is written whole
+DUMP_SAMPLE_ROWS = 2048       # of a larger one: this many rows of its [-1, last dim] view
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """Write the tensors the step returned (``eng.forward``'s dict: call probabilities, genotype
+    probabilities, the hidden states before and after the encoder, the AF rows it echoes) as
+    ``path/<name>.npy``, float32.  An output above DUMP_FULL_BYTES is written as a fixed sample of its rows (seeded,
+    the same rows in every run, in ascending order); ``x_all`` is left out, h1_after and
+    h2_after are its two halves."""
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name in sorted(out):
+        t = out[name]
+        if name == "x_all" or not torch.is_tensor(t):
+            continue
+        if t.numel() * 4 > DUMP_FULL_BYTES:
+            t = t.reshape(-1, t.shape[-1])
+            rows = np.sort(np.random.default_rng(20240).choice(t.shape[0], DUMP_SAMPLE_ROWS, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = t.detach().float().cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {name} takes the dump past {DUMP_LIMIT_BYTES} bytes"
+        np.save(d / f"{name}.npy", a)
+
+
+def knn_probes(wl, eng, k, cap):
+    """The kNN search alone, outside the timed region -> (search ms, HBM-regime probe)."""
+    from src import native as N
+    lib, P = N.lib(), eng.packed()
+    index, tok, site_mask = wl.index, wl.tok, wl.site_mask
+    # the whole kNN search (LUT + pre-pass + scan + merges + decode)
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    search = make_search(wl, eng, k)
+    ev0.record()
+    for _ in range(5):
+        search()
+    ev1.record()
+    torch.cuda.synchronize()
+    knn_ms = ev0.elapsed_time(ev1) / 5
+    # HBM-regime probes (SURVEY.md §8d states the HBM target at Bq in {48, 96}): the scan
+    # streams the panel once per launch; up to ~150 queries the int8 MFMA work per code
+    # byte is below the HBM ridge
+    probes = []
+    for nq in (48, 96, 128):
+        tq = tok[:nq].contiguous()
+        index.search(tq, P.W, site_mask, k)
+        lib.snvrag_evlog_enable(cap)
+        for _ in range(5):
+            index.search(tq, P.W, site_mask, k)
+        torch.cuda.synchronize()
+        kk, mm, ww = np.zeros(cap, np.int32), np.zeros(cap, np.float32), np.zeros(cap, np.float64)
+        n2 = lib.snvrag_evlog_read(kk.ctypes.data, mm.ctypes.data, ww.ctypes.data, cap)
+        lib.snvrag_evlog_enable(0)
+        kk, mm, ww = kk[:n2], mm[:n2], ww[:n2]
+        sel = (kk == 4) & (ww >= 0.5 * ww[kk == 4].max())
+        pr = dict(queries=nq, avg_launch_ms=round(float(mm[sel].mean()), 4),
+                  bytes_per_launch=float(ww[sel].mean()),
+                  achieved_gbs=round(float(ww[sel].sum() / (mm[sel].sum() * 1e-3)) / 1e9, 1))
+        pr["frac"] = round(pr["achieved_gbs"] / HBM_PEAK_GBS, 4)
+        probes.append(pr)
+    probe = dict(probes[-1], per_queries=[{kq: p[kq] for kq in ("queries", "avg_launch_ms", "achieved_gbs", "frac")}
+                                          for p in probes])
+    return knn_ms, probe
 
 
 def call_agreement(o_lo, o_hi, raw_mask):

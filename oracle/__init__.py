@@ -5,7 +5,7 @@ embedding-RAG hot path, used only as the checker:
 
 * ``tests/``                      — parity tests compare the HIP path with it,
 * ``__graft_entry__.smoke()``     — one small invocation checked against it,
-* ``bench.py`` (``cpu_baseline``) — timed on the host cores as the "port" baseline.
+* ``bench.py --full`` (``cpu_baseline``) — timed on the host cores as the "port" baseline.
 
 Nothing in ``rag-snvbert_amd/`` imports, calls or links anything here; the
 product path fails loudly when the HIP library is missing instead of falling

@@ -20,9 +20,9 @@ for s in $STEPS; do
   case $s in
     gpu)   step pytest_gpu 600 python -u -m pytest tests -m gpu -q -rf --timeout 120 --timeout-method thread ${PYTEST_ARGS:-} ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py ${BENCH_ARGS:-} ;;
+    bench) step bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
     prof)  step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof/$TAG -o bench \
-             -- python3 bench.py --steps 5 --warmup 2 --cpu-baseline 0 ;;
+             -- python3 bench.py --full --steps 5 --warmup 2 --cpu-baseline 0 ;;
   esac
 done
 echo ALLOK
