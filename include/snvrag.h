@@ -414,7 +414,7 @@ int snvrag_derive(const snvrag_derive_job_t* jobs, int njobs, int64_t total_piec
  * 235).  out bf16 [M, N] (ldo) = A bf16 [M, K] (lda) W^T (+ bias f32 [N]) (+ resid bf16 [M, N]),
  * f32 accumulation, one rounding.  W bf16 [N, K] (ldw) is packed once into
  * snvrag_gemm256_pack_bytes(N, K) bytes (or by snvrag_derive kind 3).  N = 384, K % 64 == 0, rows
- * and pointers 16-byte aligned. */
+ * and pointers 16-byte aligned, M < 2^31 ("bad M" otherwise, before any launch). */
 size_t snvrag_gemm256_pack_bytes(int N, int K);
 int snvrag_gemm256_pack(int N, int K, const void* w, int64_t ldw, void* out, void* stream);
 int snvrag_gemm256_forward(int64_t M, int N, int K, const void* A, int64_t lda, const void* wpacked, const float* bias,

@@ -743,6 +743,7 @@ extern "C" int snvrag_gemm256_forward(int64_t M, int N, int K, const void* A, in
   SNV_CHECK_ARG(N == 384, "gemm256: N = 384");
   SNV_CHECK_ARG(K >= 64 && K % 64 == 0, "gemm256: K % 64 == 0");
   SNV_CHECK_ARG(A && wpacked && out, "null pointer");
+  SNV_CHECK_ARG(M < (1L << 31), "bad M");              // (G2Args carries M as int)
   SNV_CHECK_ARG(M >= 0 && lda >= K && ldo >= N && (!resid || ld_resid >= N), "bad shape / leading dims");
   SNV_CHECK_ARG(lda % 8 == 0 && ldo % 8 == 0 && (!resid || ld_resid % 8 == 0), "16-byte rows");
   SNV_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)wpacked % 16) == 0 &&
@@ -785,6 +786,7 @@ extern "C" int snvrag_gemm256_ln_forward(int64_t M, int N, int K, const void* A,
   SNV_CHECK_ARG(N == 384, "gemm256: N = 384");
   SNV_CHECK_ARG(K >= 64 && K % 64 == 0, "gemm256: K % 64 == 0");
   SNV_CHECK_ARG(A && wpacked && out && ln_g && ln_b, "null pointer");
+  SNV_CHECK_ARG(M < (1L << 31), "bad M");
   SNV_CHECK_ARG(M >= 0 && lda >= K && ldo >= N && (!base || ld_base >= N), "bad shape / leading dims");
   SNV_CHECK_ARG(post_af_period >= 0, "bad af period");
   SNV_CHECK_ARG(lda % 8 == 0 && ldo % 8 == 0 && (!base || ld_base % 8 == 0), "16-byte rows");

@@ -21,9 +21,9 @@ def lut_wide_flag(lut: torch.Tensor, nq: int, n_sites_pad: int) -> int:
     return int(lut.cpu().numpy().view(np.int8)[nqt * 3 * KS * 1024 + nqt * 64:][:4].view(np.int32)[0])
 
 
-def rand_case(n_ref, n_sites, nq, seed, tie_heavy=False, D=64):
-    """Random panel + queries copied from panel rows with 5 % flips; query tokens over L = 1030
-    (``tie_heavy``: half the panel identical, aligned masks; otherwise a few extra query-masked sites)."""
+def rand_case(n_ref, n_sites, nq, seed, tie_heavy=False, D=64, L=1030):
+    """Random panel + queries copied from panel rows with 5 % flips; query tokens over L positions
+    (L >= n_sites + 2;``tie_heavy``: half the panel identical, aligned masks; otherwise a few extra query-masked sites)."""
     rng = np.random.default_rng(seed)
     W = rng.standard_normal((12, D)).astype(np.float32)
     af = rng.beta(0.3, 3.0, n_sites)
@@ -32,7 +32,6 @@ def rand_case(n_ref, n_sites, nq, seed, tie_heavy=False, D=64):
         panel[: n_ref // 2] = panel[0]
     q_alle = panel[rng.integers(0, n_ref, nq)] ^ (rng.random((nq, n_sites)) < 0.05)
     site_mask = (rng.random(n_sites) < 0.4).astype(np.uint8)
-    L = 1030
     tok = np.zeros((nq, L), np.int64)
     tok[:, 0] = 2
     tok[:, 1:1 + n_sites] = np.where(site_mask[None] == 1, 4, 5 + q_alle)

@@ -523,6 +523,14 @@ def test_fused_mlp(M, mode):
     torch.testing.assert_close(out.float(), ref, rtol=1e-2, atol=2e-2)
 
 
+def _afgate_ref(af, afp, ag, rs, D=384):
+    """CrossAFInteraction (fusion.py:82-86) in torch fp32, rounded to bf16 as the MLP's input is."""
+    c = torch.stack([af, afp], -1)
+    gate = torch.sigmoid(torch.nn.functional.gelu(c @ ag[0].t() + ag[1]) @ ag[2].t() + ag[3])
+    enc = torch.nn.functional.gelu(torch.nn.functional.layer_norm(c @ ag[4].t() + ag[5], (D,), ag[6], ag[7], 1e-5))
+    return (af[:, None] + rs * gate * enc).to(torch.bfloat16).float()
+
+
 @pytest.mark.parametrize("M", [1030, 77, 1])
 def test_mlp_afgate_vs_fp32_and_two_launch_path(M):
     """snvrag_mlp_afgate_forward (CrossAFInteraction computed in the af_adapter MLP's prologue:
@@ -542,10 +550,7 @@ def test_mlp_afgate_vs_fp32_and_two_launch_path(M):
     mv = torch.cat([b1, b2]).contiguous()
     ws = K().mlp_pack(w1, w2)
     # torch fp32 reference
-    c = torch.stack([af, afp], -1)
-    gate = torch.sigmoid(torch.nn.functional.gelu(c @ ag[0].t() + ag[1]) @ ag[2].t() + ag[3])
-    enc = torch.nn.functional.gelu(torch.nn.functional.layer_norm(c @ ag[4].t() + ag[5], (D,), ag[6], ag[7], 1e-5))
-    fa = (af[:, None] + rs * gate * enc).to(torch.bfloat16).float()
+    fa = _afgate_ref(af, afp, ag, rs)
     h = torch.nn.functional.gelu(fa @ w1.float().t() + b1).to(torch.bfloat16).float()
     ref = torch.sigmoid(h @ w2.float().t() + b2)
     frags, vec = K().mlp_afgate_pack(ag, mv)
@@ -814,3 +819,308 @@ def test_gemm256_row_groups_bit_identical(groups):
     assert torch.equal(y, ref) and torch.equal(y1, ref)
     e = (ref.float() - (a.float() @ w.float().t() + b + r.float())).abs()
     assert e.max().item() < 0.1
+
+
+# ------------------------------------------- launch-size branches past the bench's switch points --
+def _n_cu() -> int:
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+@pytest.mark.parametrize("Kd,lda_pad,bias,res", [(1536, 0, True, False), (1152, 0, False, True), (1152, 8, True, True)])
+def test_gemm256_multi_round_vs_fp32(Kd, lda_pad, bias, res):
+    """Plain-epilogue snvrag_gemm256_forward past one round of workgroups: M = 8 * 32 * n_cu + 4465
+    (70 001 on 256 CUs) crosses g3_groups' `M > 8 * 32 * n_cu` (csrc/gemm256.hip), where the
+    workgroup height comes from the cost search over G = 4..8 (the G = 5..7 instantiations), with a
+    ragged last workgroup; test_gemm256_vs_fp32's bar, unchanged.  The default launch is
+    bit-identical to every forced height and to the v1 kernel (g2_variant 4) at the same M."""
+    kk = K()
+    M = 8 * 32 * _n_cu() + 4465
+    assert M > 8 * 32 * _n_cu()
+    g = torch.Generator(device=DEV).manual_seed(M + Kd + lda_pad)
+    a = torch.randn(M, Kd + lda_pad, device=DEV, generator=g).to(torch.bfloat16)[:, :Kd]
+    w = (torch.randn(384, Kd, device=DEV, generator=g) / math.sqrt(Kd)).to(torch.bfloat16)
+    b = torch.randn(384, device=DEV, generator=g) if bias else None
+    r = torch.randn(M, 384, device=DEV, generator=g).to(torch.bfloat16) if res else None
+    assert a.stride(0) == Kd + lda_pad
+    ref = a.float() @ w.float().t()
+    if b is not None:
+        ref = ref + b
+    if r is not None:
+        ref = ref + r.float()
+    wp = kk.gemm256_pack(w)
+    out = kk.gemm256(a, wp, 384, bias=b, resid=r)
+    tol = _bf16_step(ref) + 1e-4 * (1 + ref.abs())
+    bad = (out.float() - ref).abs() > tol
+    assert int(bad.sum()) == 0, f"{int(bad.sum())} of {bad.numel()} outside one bf16 step, first at " \
+                                f"{bad.nonzero()[:4].tolist()}"
+    if r is not None:                                 # in place: out aliases the residual
+        r2 = r.clone()
+        kk.gemm256(a, wp, 384, bias=b, resid=r2, out=r2)
+        assert torch.equal(r2, out)
+    try:
+        for groups in (4, 5, 6, 7, 8):
+            kk.set_option("g2_groups", groups)
+            assert torch.equal(kk.gemm256(a, wp, 384, bias=b, resid=r), out), groups
+        kk.set_option("g2_groups", 0)
+        kk.set_option("g2_variant", 4)
+        assert torch.equal(kk.gemm256(a, wp, 384, bias=b, resid=r), out)
+    finally:
+        kk.set_option("g2_groups", 0)
+        kk.set_option("g2_variant", 0)
+
+
+def test_gemm256_rejects_m_past_int32():
+    """Both gemm256 entries carry M as int inside: M = 2^31 is refused with "bad M" before any
+    launch (as snvrag_mlp_afgate_forward does), not truncated."""
+    nn = N()
+    lib = nn.lib()
+    a = torch.zeros(1, 64, device=DEV, dtype=torch.bfloat16)
+    wp = torch.zeros(int(lib.snvrag_gemm256_pack_bytes(384, 64)), device=DEV, dtype=torch.uint8)
+    out = torch.zeros(1, 384, device=DEV, dtype=torch.bfloat16)
+    gm, be = torch.ones(384, device=DEV), torch.zeros(384, device=DEV)
+    rc = lib.snvrag_gemm256_forward(2 ** 31, 384, 64, nn.ptr(a), 64, nn.ptr(wp), None, None, 0, nn.ptr(out), 384,
+                                    nn.stream_ptr())
+    assert rc != 0 and lib.snvrag_last_error().decode() == "snvrag_gemm256_forward: bad M"
+    rc = lib.snvrag_gemm256_ln_forward(2 ** 31, 384, 64, nn.ptr(a), 64, nn.ptr(wp), None, nn.ptr(gm), nn.ptr(be),
+                                       1e-5, None, 0, 1.0, None, 0, nn.ptr(out), 384, nn.stream_ptr())
+    assert rc != 0 and lib.snvrag_last_error().decode() == "snvrag_gemm256_ln_forward: bad M"
+    torch.cuda.synchronize()
+    assert (out == 0).all()
+
+
+# First-round stagger ("desync"): workgroups 0..255 of a large grid wait (blockIdx / 8) % 8 steps of
+# s_memtime before their first barrier.  Each builder below returns (option, M, rows per workgroup,
+# run() -> output, check(output rows, rows)) at the smallest M past its launcher's own condition,
+# plus a ragged remainder; D = 384 (the bench's width).
+def _rn(g):
+    return lambda *s, sc=1.0: torch.randn(*s, device=DEV, generator=g) * sc
+
+
+def _stagger_tail(entry):
+    kk, D, bf, F = K(), 384, torch.bfloat16, torch.nn.functional
+    if entry == "persist":
+        # csrc/tail.hip launch_tailp `ntiles >= 8L * grid` (grid = one workgroup per CU) and
+        # tailp_kernel's `ntiles % G != 0` (only the workgroups with one tile fewer wait)
+        ntiles = 8 * _n_cu() + 5
+        assert ntiles >= 8 * _n_cu() and ntiles % _n_cu() != 0
+    else:
+        # csrc/tail.hip launch_tail `nwg >= 8 * 256`: the wide-row launch (tail_wide = 1) and
+        # tail_kernel (tail_wide = 0; the FFN-only entry takes the same line)
+        ntiles = 8 * 256
+        assert ntiles >= 8 * 256
+    M = 128 * (ntiles - 1) + 77
+    rn = _rn(torch.Generator(device=DEV).manual_seed(M))
+    x, att = rn(M, D).to(bf), rn(M, D, sc=0.5).to(bf)
+    w_o, b_o = (rn(D, D) / math.sqrt(D)).to(bf), rn(D, sc=0.1)
+    g1, be1 = 1 + rn(D, sc=0.2), rn(D, sc=0.1)
+    w1, w2 = (rn(4 * D, D) / math.sqrt(D)).to(bf), rn(D, 4 * D) / math.sqrt(4 * D)
+    b1, b2 = rn(4 * D), rn(D)
+    gf, bff = 1 + rn(4 * D, sc=0.2), rn(4 * D, sc=0.1)
+    g2, be2 = 1 + rn(D, sc=0.2), rn(D, sc=0.1)
+    w2g, b2g, _ = kk.fold_layernorm(w2, b2, gf, bff, bf)
+    vec = kk.ffn_vec(b1, b2g, w2g, g2, be2)
+    ts = kk.tail_pack(w_o, w1, w2g)
+
+    def run():
+        if entry == "ffn":
+            return kk.tail_ffn_forward(x, ts, vec)
+        with kk.option("tail_wide", int(entry == "wide")), kk.option("tail_persist", int(entry == "persist")):
+            return kk.tail_forward(att, x.clone(), ts, b_o, g1, be1, vec)
+
+    def check(out, rows):                               # test_tail32_kernel / test_tail_wide_kernel's bar
+        x1 = x[rows].double()
+        if entry != "ffn":
+            x1 = F.layer_norm(x1 + att[rows].double() @ w_o.double().T + b_o.double(), (D,), g1.double(),
+                              be1.double(), 1e-5)
+        h = F.leaky_relu(x1 @ w1.double().T + b1.double(), 0.1)
+        hn = F.layer_norm(h, (4 * D,), gf.double(), bff.double(), 1e-5)
+        f = F.leaky_relu(hn @ w2.double().T + b2.double(), 0.1)
+        ref = F.layer_norm(x1 + f, (D,), g2.double(), be2.double(), 1e-5)
+        torch.testing.assert_close(out.double(), ref, rtol=5e-2, atol=5e-2)
+        assert (out.double() - ref).abs().mean() < 1e-2
+
+    return "tail_desync", M, 128, run, check
+
+
+def _stagger_sgemm(waves):
+    kk, nn, D = K(), N(), 384
+    # csrc/sgemm.hip sg_launch `cdiv(M, 32 * WAVES) >= 4 * 256`: the 4-wave LayerNorm form and the
+    # 8-wave plain projection
+    M = 32 * waves * (4 * 256 - 1) + 77
+    assert -(-M // (32 * waves)) >= 4 * 256
+    rn = _rn(torch.Generator(device=DEV).manual_seed(M))
+    x = rn(M, D).to(torch.bfloat16)
+    w, b = (rn(D, D) / math.sqrt(D)).to(torch.bfloat16), rn(D)
+    gm, bt = rn(D).abs() + 0.5, rn(D)
+    ws = kk.sgemm_pack(w)
+    ln = waves == 4
+
+    def run():
+        if ln:
+            return kk.sgemm(x, ws, D, kk.sgemm_vec(b, ln=(gm, bt)), epi=kk.SG_LN, act=nn.ACT_LRELU, slope=0.1)
+        return kk.sgemm(x, ws, D, kk.sgemm_vec(b), act=nn.ACT_NONE)
+
+    def check(out, rows):                               # test_stream_gemm's bar
+        ref = x[rows].float() @ w.float().t() + b
+        if ln:
+            ref = torch.nn.functional.layer_norm(torch.nn.functional.leaky_relu(ref, 0.1) + x[rows].float(), (D,),
+                                                 gm, bt, 1e-5)
+        torch.testing.assert_close(out.float(), ref, rtol=1e-2, atol=2e-2)
+
+    return "sg_desync", M, 32 * waves, run, check
+
+
+def _stagger_mlp(afgate):
+    kk, D, H = K(), 384, 1536
+    # csrc/sgemm.hip mlp_launch `cdiv(a.M, 128) >= 4 * 256` (both the plain and the AF-gate form)
+    M = 128 * (4 * 256 - 1) + 77
+    assert -(-M // 128) >= 4 * 256
+    rn = _rn(torch.Generator(device=DEV).manual_seed(M + afgate))
+    w1, w2 = (rn(H, D) / math.sqrt(D)).to(torch.bfloat16), (rn(D, H) / math.sqrt(H)).to(torch.bfloat16)
+    b1, b2 = rn(H), rn(D, sc=0.1)
+    mv = torch.cat([b1, b2]).contiguous()
+    ws = kk.mlp_pack(w1, w2)
+    if afgate:
+        ag = [rn(32, 2, sc=0.8), rn(32, sc=0.1), rn(D, 32, sc=0.25), rn(D, sc=0.1), rn(D, 2, sc=0.7), rn(D, sc=0.1),
+              1 + rn(D, sc=0.1), rn(D, sc=0.1)]
+        rs = 0.37
+        af, afp = torch.sigmoid(rn(M, sc=2.0)), torch.sigmoid(rn(M, sc=2.0))
+        frags, vec = kk.mlp_afgate_pack(ag, mv)
+        run = lambda: kk.mlp_afgate(af, afp, frags, rs, ws, vec)
+    else:
+        x = rn(M, D).to(torch.bfloat16)
+        run = lambda: kk.mlp(x, ws, mv, epi2=0)
+
+    def check(out, rows):                               # test_fused_mlp / test_mlp_afgate's bar
+        xin = _afgate_ref(af[rows], afp[rows], ag, rs) if afgate else x[rows].float()
+        h = torch.nn.functional.gelu(xin @ w1.float().t() + b1).to(torch.bfloat16).float()
+        torch.testing.assert_close(out.float(), torch.sigmoid(h @ w2.float().t() + b2), rtol=1e-2, atol=2e-2)
+
+    return "mlp_desync", M, 128, run, check
+
+
+def _stagger_gemm256(ln):
+    kk, Kd = K(), 1536
+    # csrc/gemm256.hip g3_launch `cdiv(a.M, 32 * G) >= 4 * 256` with the height forced to G = 4
+    M = 128 * 1024 + 1
+    assert -(-M // (32 * 4)) >= 4 * 256
+    rn = _rn(torch.Generator(device=DEV).manual_seed(M + ln))
+    a = rn(M, Kd).to(torch.bfloat16)
+    w, b = (rn(384, Kd) / math.sqrt(Kd)).to(torch.bfloat16), rn(384)
+    r = rn(M, 384).to(torch.bfloat16)
+    gm, be = 1 + rn(384, sc=0.2), rn(384, sc=0.1)
+    af = torch.sigmoid(rn(M, sc=2.0))
+    wp = kk.gemm256_pack(w)
+
+    def run():
+        with kk.option("g2_groups", 4):
+            if ln:
+                return kk.gemm256_ln(a, wp, b, (gm, be), base=r, post_scale=0.37, post_af=af)
+            return kk.gemm256(a, wp, 384, bias=b, resid=r)
+
+    def check(out, rows):                               # test_gemm256_vs_fp32 / test_gemm256_ln_vs_fp32's bar
+        ref = a[rows].float() @ w.float().t() + b
+        if ln:
+            ai = af[rows]
+            mw = torch.log1p(1.0 / (torch.minimum(ai, 1 - ai) + 1e-6)).clamp(max=3.0)
+            ref = r[rows].float() + 0.37 * torch.nn.functional.layer_norm(ref, (384,), gm, be, 1e-5) * mw[:, None]
+        else:
+            ref = ref + r[rows].float()
+        tol = _bf16_step(ref) + (1e-3 if ln else 1e-4) * (1 + ref.abs())
+        bad = (out.float() - ref).abs() > tol
+        assert int(bad.sum()) == 0, f"{int(bad.sum())} of {bad.numel()} outside tolerance"
+
+    return "g2_desync", M, 128, run, check
+
+
+def _stagger_projw():
+    kk, D = K(), 384
+    # csrc/tail.hip snvrag_proj_forward `cdiv(M, TL_ROWS) >= 8 * 256` (the wide-row projection)
+    M = 128 * (8 * 256 - 1) + 77
+    assert -(-M // 128) >= 8 * 256
+    rn = _rn(torch.Generator(device=DEV).manual_seed(M))
+    x = rn(M, D).to(torch.bfloat16)
+    w, b = (rn(D, D) / math.sqrt(D)).to(torch.bfloat16), rn(D)
+    ws = kk.proj_pack(w)
+
+    def run():
+        with kk.option("proj_wide", 1):
+            return kk.proj_forward(x, ws, b, 1)
+
+    def check(out, rows):                               # test_proj_kernel_vs_fp64's bar
+        torch.testing.assert_close(out.double(), x[rows].double() @ w.double().T + b.double(), rtol=2e-2, atol=2e-2)
+
+    return "sg_desync", M, 128, run, check
+
+
+_STAGGER = {
+    "tail_wide": lambda: _stagger_tail("wide"), "tail": lambda: _stagger_tail("tail"),
+    "tail_ffn": lambda: _stagger_tail("ffn"), "tail_persist": lambda: _stagger_tail("persist"),
+    "sgemm_ln_4w": lambda: _stagger_sgemm(4), "sgemm_8w": lambda: _stagger_sgemm(8),
+    "mlp": lambda: _stagger_mlp(False), "mlp_afgate": lambda: _stagger_mlp(True),
+    "gemm256": lambda: _stagger_gemm256(False), "gemm256_ln": lambda: _stagger_gemm256(True),
+    "proj_wide": _stagger_projw,
+}
+
+
+@pytest.mark.parametrize("family", list(_STAGGER))
+def test_first_round_stagger_changes_no_bit(family):
+    """The first-round stagger prologue (a timed wait in workgroups 0..255, ahead of the first
+    barrier) of every family that has one, at an M past the launcher's own switch (cited and
+    asserted in the family's builder above): the output with the default stagger (option -1) is
+    bit-identical to the output with the stagger off (0) and with another step (3000 cycles), and
+    the rows of the first 256 workgroups and of the last (ragged) tile meet the family's existing
+    reference bar (the reference is computed on those rows only)."""
+    kk = K()
+    opt, M, R, run, check = _STAGGER[family]()
+    outs = {}
+    for v in (-1, 0, 3000):
+        with kk.option(opt, v):
+            outs[v] = run()
+    assert outs[-1].shape[0] == M
+    assert torch.equal(outs[-1], outs[0])
+    assert torch.equal(outs[-1], outs[3000])
+    assert M > 257 * R and M % R != 0
+    rows = torch.cat([torch.arange(0, 256 * R), torch.arange((M - 1) // R * R, M)]).to(DEV)
+    check(outs[-1][rows], rows)
+
+
+# ------------------------------------------------------ v1 scan kernel (rows of 64 k sites) --
+@pytest.mark.parametrize("limbs", [1, 2])
+@pytest.mark.parametrize("k", [1, 32])
+@pytest.mark.parametrize("nq", [5, 70])
+@pytest.mark.parametrize("n_ref", [33, 3001])
+@pytest.mark.parametrize("n_sites,n_sites_pad", [(60, 64), (300, 320), (570, 576), (1080, 1088)])
+def test_knn_v1_scan_bit_exact_vs_oracle(n_sites, n_sites_pad, n_ref, nq, k, limbs):
+    """scan_kernel<KSM, LB> (csrc/knn.hip), the path snvrag_knn_scan takes when
+    `n_sites_pad % 256 != 0` — include/snvrag.h promises n_sites_pad % 64 == 0 only, but
+    PanelIndex pads to 256, so no other test reaches it.  knn_lut + knn_scan + topk_merge called
+    directly with codes rows of exactly n_sites_pad bytes (ld_codes == n_sites_pad), KS = 1 / 5 /
+    9 / 17 = the SCAN(4 / 8 / 16 / 17) instantiations, a ragged second query tile (nq = 70), a
+    ragged last range, both limb counts, one tie-heavy case per width; LUT and keys equal the
+    oracle's bit for bit, as in test_knn_bit_exact_vs_oracle.  Where the panel has 16 k rows, also
+    with a non-zero ref_offset from the strict threshold of a panel prefix (knn_threshold)."""
+    kk = K()
+    assert n_sites_pad % 64 == 0 and n_sites_pad % 256 != 0
+    tie = n_ref == 3001 and nq == 70 and k == 32
+    W, panel, site_mask, tok = _rand_case(n_ref, n_sites, nq, n_sites + n_ref + 3 * nq + k + limbs, tie, L=n_sites + 6)
+    codes_h = np.zeros((n_ref, n_sites_pad), np.uint8)
+    codes_h[:, :n_sites] = panel
+    codes = torch.from_numpy(codes_h).to(DEV)
+    lut, exps, _ = kk.knn_lut(torch.from_numpy(tok).to(DEV), torch.from_numpy(W).to(DEV),
+                              torch.from_numpy(site_mask).to(DEV), n_sites, n_sites_pad, limbs)
+    dq_o, e_o = knn_np.quantize_lut(knn_np.lut_delta_f32(W, tok, site_mask), limbs)
+    dq_g = decode_lut(lut, nq, n_sites_pad, limbs)
+    np.testing.assert_array_equal(exps.cpu().numpy(), e_o)
+    np.testing.assert_array_equal(dq_g[:, :n_sites], dq_o)
+    assert (dq_g[:, n_sites:] == 0).all()
+    oi, od = knn_np.knn(panel, dq_o, k)
+    assert (oi >= 0).all()
+    keys = kk.topk_merge(kk.knn_scan(codes, n_sites_pad, lut, nq, limbs, k), k)
+    np.testing.assert_array_equal(keys.cpu().numpy().view(np.uint64), knn_np.pack_key(od, oi))
+    if n_ref >= 16 * k:
+        off = 70_000
+        pre = kk.knn_scan(codes[:16 * k], n_sites_pad, lut, nq, limbs, k, off, n_parts=2)
+        th = kk.knn_threshold(kk.topk_merge(pre, k), k)
+        keys2 = kk.topk_merge(kk.knn_scan(codes, n_sites_pad, lut, nq, limbs, k, off, th_init=th), k)
+        np.testing.assert_array_equal(keys2.cpu().numpy().view(np.uint64), knn_np.pack_key(od, oi + off))
