@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SNVRAG_ABI_VERSION 28
+#define SNVRAG_ABI_VERSION 29
 
 enum { SNVRAG_F32 = 0, SNVRAG_BF16 = 1 };
 enum { SNVRAG_ACT_NONE = 0, SNVRAG_ACT_GELU = 1, SNVRAG_ACT_LRELU = 2, SNVRAG_ACT_SIGMOID = 3 };
@@ -37,7 +37,12 @@ int snvrag_device_info(int device, char* name, int name_len);
  * counterpart: knn_no_reduce, scan_mode, scan_nt, unfused_ln, encoder_chunk, gemm_tile128,
  * gemm_nw, tail_variant, tail_desync, sg_desync, sg_waves4, ln_bwd_nopf, attn_variant.  Each
  * starts from the environment variable SNVRAG_<NAME> (read once, at first use); launches read
- * the table. */
+ * the table.
+ * deterministic (default 0) is the one switch meant for users: 1 makes the Python wrappers
+ * (src/kernels.py) route the weight gradients, the neighbour-mean backward and the focal loss to
+ * the fixed-order *_det entry points below, so two runs of a training step on the same inputs
+ * give the same bits (the reference trains with PyTorch's default, non-deterministic, kernels:
+ * pretrain_with_val_optimized.py:235). */
 int snvrag_set_option(const char* name, int64_t value);
 int snvrag_get_option(const char* name, int64_t* value);
 
@@ -487,6 +492,16 @@ int snvrag_attention_bwd(int64_t nseq, int64_t L, int heads, int dh, const void*
  * weight * dFL/dprobs (0 on unmasked rows). */
 int snvrag_focal_loss(int64_t M, int C, const float* probs, const int64_t* labels, const uint8_t* mask,
                       float gamma, float weight, float* loss_sum, float* grad, void* stream);
+/* The same loss (FocalLoss.forward, main/optim_schedule.py:64-96, reduction='sum' over the masked
+ * rows of pretrain_with_val_optimized.py:215-217) and the same grad with a fixed summation order
+ * instead of one float atomic per block: block b of 256 rows writes its sum to ws[b] (wave
+ * butterfly over lane distances 32, 16, .. 1, then the four wave sums left to right) and one thread
+ * adds ws[0], ws[1], .. in index order, then *loss_sum += that sum.  ws: a caller-owned buffer of
+ * snvrag_focal_loss_det_ws_bytes(M) bytes, never shared between streams. */
+size_t snvrag_focal_loss_det_ws_bytes(int64_t M);
+int snvrag_focal_loss_det(int64_t M, int C, const float* probs, const int64_t* labels, const uint8_t* mask,
+                          float gamma, float weight, float* loss_sum, float* grad, float* ws, size_t ws_bytes,
+                          void* stream);
 /* acc = sum x^2 in a fixed reduction order (bit-identical for identical x). x 16-byte aligned.
  * snvrag_sqnorm keeps its per-block partials in one process-wide device buffer: one call in flight
  * per device (stream-ordered); snvrag_sqnorm_ws takes a caller-owned workspace of
@@ -545,6 +560,16 @@ int snvrag_nbr_mean_drop_bwd(int64_t nq, int k, int64_t L, int D, int n_sites, i
                              const int32_t* inv, const uint8_t* codes, const float* W, const float* pe,
                              const float* Ar, float p, uint64_t seed, int tok0, int sos, int eos, int pad,
                              const float* dout, float* dW, float* dAr, void* stream);
+/* The same backward (the train-mode neighbour re-encoding of embedding_rag_dataset.py:404-417 under
+ * bert.py:176-179's dropout) without float atomics: position block l stores its [V, D] partial of
+ * the token-table gradient to ws[l] and a fixed-order column sum over l is added into dW (the
+ * <pad> row receives zeros); dAr as above (one thread per element).  ws: a caller-owned buffer of
+ * snvrag_nbr_mean_drop_bwd_det_ws_bytes(L, V, D) = L V D floats, never shared between streams. */
+size_t snvrag_nbr_mean_drop_bwd_det_ws_bytes(int64_t L, int V, int D);
+int snvrag_nbr_mean_drop_bwd_det(int64_t nq, int k, int64_t L, int D, int n_sites, int64_t ld_codes, int V,
+                                 const int32_t* inv, const uint8_t* codes, const float* W, const float* pe,
+                                 const float* Ar, float p, uint64_t seed, int tok0, int sos, int eos, int pad,
+                                 const float* dout, float* dW, float* dAr, void* ws, size_t ws_bytes, void* stream);
 size_t snvrag_ln_bwd_ws_bytes(int64_t M, int N);
 int snvrag_ln_bwd(int64_t M, int N, const void* dy, const void* s, const float* stats, const float* g,
                   void* ds, void* dres, float* dg, float* db, int accumulate, float p_r, float p_out,
@@ -571,6 +596,22 @@ int snvrag_linear_dw(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ld
 int snvrag_linear_dw_parts(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x,
                            int64_t ldx, int n_parts, float* const* dw_parts, float* const* db_parts, int splits,
                            void* stream);
+/* The two launches above (the nn.Linear backward of pretrain_with_val_optimized.py:235) with a
+ * summation order fixed by (M, N, K, splits) alone: the same MFMA main loop, but chunk zc of the S
+ * chunks stores its tile to ws[zc][n][k] (and its bias partial to ws_b[zc][n] behind the S N K tile
+ * floats) with plain stores, and a second kernel computes
+ *   dw[i] += ws[0][i] + ws[1][i] + ... + ws[S - 1][i]        (db likewise)
+ * in that order for every output part.  The result does not depend on which workgroup ran a
+ * chunk (option dw_xcd) nor on their timing.  dw / db are still ACCUMULATED into and must be
+ * 16-byte aligned.  ws: a caller-owned, 16-byte aligned buffer of
+ * snvrag_linear_dw_det_ws_bytes(M, N, K, splits) = S (N K + N) floats, reusable by consecutive
+ * launches of one stream and never shared between streams. */
+size_t snvrag_linear_dw_det_ws_bytes(int64_t M, int64_t N, int64_t K, int splits);
+int snvrag_linear_dw_det(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x, int64_t ldx,
+                         float* dw, float* db, int splits, void* ws, size_t ws_bytes, void* stream);
+int snvrag_linear_dw_parts_det(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x,
+                               int64_t ldx, int n_parts, float* const* dw_parts, float* const* db_parts,
+                               int splits, void* ws, size_t ws_bytes, void* stream);
 
 /* Inference post-processing (replaces infer_embedding_rag.py:145-152): probs_h1/h2 [M, 2]
  * f32 head probabilities -> p1, p2 [M] = softmax(probs)[..., 1] (the reference's second

@@ -82,6 +82,9 @@ struct Options {
                            // 0.62 vs 0.68 ms, bit-identical); 0: tail.hip PROJ mode
   int64_t tail_wide;       // block tail at D = 384 (PRE): 1 (default) the wide-row form (tailw.hip), 0 tail_kernel,
                            // 2 the wide-row form with phase stamps into the snvrag_tail_stamps buffer
+  int64_t deterministic;   // 1: the Python wrappers route dW, the neighbour-mean backward and the focal loss to the
+                           // fixed-order *_det entry points (no float atomics); 0 (default): the atomic forms.
+                           // Read by src/kernels.py, not by a launch path: each entry point is one form
 };
 Options& options();
 // the diagnostic stamp buffer set by snvrag_tail_stamps (null unless a tool set one)

@@ -53,9 +53,15 @@ struct DwOut {
 // lane (the LDS side of a DMA piece is contiguous) and rows past the chunk read the buffer's zeros.
 constexpr int DWD_NS = 4;
 
+//
+// DET (the deterministic training mode): the same main loop, but chunk zc stores its tile with
+// plain vector stores to the workspace ws[zc][n][k] (and the k0 == 0 tiles their bias partial to
+// ws_b[zc][n], ws_b = ws + S N K) instead of adding into the output; dw_reduce_kernel then sums the
+// S partials of every element in chunk order.  Which workgroup runs a chunk (xcd_map) moves no sum.
+template <bool DET>
 __global__ __launch_bounds__(256) void dw_dma_kernel(int M, int N, int K, const bf16* __restrict__ dy, long ldy,
                                                      const bf16* __restrict__ x, long ldx, DwOut out, int chunk,
-                                                     int xcd_map) {
+                                                     int xcd_map, float* __restrict__ ws) {
   // one __shared__ object per ring slot, filled by the inline-asm DMA (dma_x4): the compiler's
   // waitcnt pass does not track LDS-DMA across the loop back-edge (with the builtin it still put a
   // vmcnt(0) before the first slot's reads of every ring cycle, draining the ring once per cycle);
@@ -189,16 +195,55 @@ __global__ __launch_bounds__(256) void dw_dma_kernel(int M, int N, int K, const 
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int nn = n0 + 64 * wn + 32 * a + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
-        unsafeAtomicAdd(dw + (long)(nn - nbase) * K + kk, acc[a][b][e]);
+        if constexpr (DET) ws[((long)zc * N + nn) * K + kk] = acc[a][b][e];
+        else unsafeAtomicAdd(dw + (long)(nn - nbase) * K + kk, acc[a][b][e]);
       }
     }
   if (do_db) {
+    const long S = gridDim.x / ntile;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
       const float v = dbs[a] + __shfl_xor(dbs[a], 32, 64);
-      if (lane < 32) unsafeAtomicAdd(db + (n0 - nbase) + 64 * wn + 32 * a + lane, v);
+      if (lane < 32) {
+        if constexpr (DET) ws[S * N * K + (long)zc * N + n0 + 64 * wn + 32 * a + lane] = v;
+        else unsafeAtomicAdd(db + (n0 - nbase) + 64 * wn + 32 * a + lane, v);
+      }
     }
   }
+}
+
+// The second kernel of the deterministic dW: out[i] += ws[0][i] + ws[1][i] + ... + ws[S - 1][i], the
+// partials summed in chunk order and the prior value of the output added last, for the N K weight
+// elements and (n4 > 0) the N bias entries behind them; element n of either lives in part n / seg
+// of the output buffers.  One thread per 16 B, one pass, no LDS: S independent 16-B loads per
+// thread, coalesced across the wave (bandwidth-bound: S N K f32 read once).
+__device__ __forceinline__ float* dw_part(float* const (&p)[4], int i) {
+  return i == 0 ? p[0] : i == 1 ? p[1] : i == 2 ? p[2] : p[3];
+}
+__global__ __launch_bounds__(256) void dw_reduce_kernel(int S, long nk4, long n4, int K, const float* __restrict__ ws,
+                                                        DwOut out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nk4 + n4) return;
+  const f32x4* src;
+  f32x4* dst;
+  long stride;
+  if (i < nk4) {
+    const long per = (long)out.seg * K / 4;            // 16-B units per output part
+    const int part = (int)(i / per);
+    src = reinterpret_cast<const f32x4*>(ws) + i;
+    dst = reinterpret_cast<f32x4*>(dw_part(out.w, part)) + (i - part * per);
+    stride = nk4;
+  } else {
+    const long j = i - nk4, per = out.seg / 4;
+    const int part = (int)(j / per);
+    src = reinterpret_cast<const f32x4*>(ws) + (long)S * nk4 + j;
+    dst = reinterpret_cast<f32x4*>(dw_part(out.b, part)) + (j - part * per);
+    stride = n4;
+  }
+  f32x4 s = src[0];
+#pragma unroll 4
+  for (int z = 1; z < S; ++z) s += src[z * stride];
+  *dst = *dst + s;
 }
 
 }  // namespace snvrag
@@ -219,16 +264,49 @@ extern "C" int snvrag_dw_splits(int64_t M, int64_t N, int64_t K) {
   return (int)s;
 }
 
+// rows per chunk and the number of (non-empty) chunks: a function of (M, N, K, splits) alone
+static void dw_chunks(int64_t M, int64_t N, int64_t K, int splits, int& chunk, int& S) {
+  if (splits <= 0) splits = snvrag_dw_splits(M, N, K);
+  chunk = (int)((((M + splits - 1) / splits) + DW_R - 1) / DW_R * DW_R);
+  S = (int)((M + chunk - 1) / chunk);
+}
+
 static int launch_dw(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x, int64_t ldx,
                      const DwOut& out, int splits, hipStream_t s) {
   if (M == 0) return 0;
-  if (splits <= 0) splits = snvrag_dw_splits(M, N, K);
-  const int chunk = (int)((((M + splits - 1) / splits) + DW_R - 1) / DW_R * DW_R);
-  const int S = (int)((M + chunk - 1) / chunk);
+  int chunk, S;
+  dw_chunks(M, N, K, splits, chunk, S);
   evlog_begin(s);
-  hipLaunchKernelGGL(dw_dma_kernel, dim3((unsigned)((N / DW_T) * (K / DW_T) * S)), dim3(256), 0, s, (int)M, (int)N,
-                     (int)K, (const bf16*)dy, (long)ldy, (const bf16*)x, (long)ldx, out, chunk,
-                     (int)options().dw_xcd);
+  hipLaunchKernelGGL(dw_dma_kernel<false>, dim3((unsigned)((N / DW_T) * (K / DW_T) * S)), dim3(256), 0, s, (int)M,
+                     (int)N, (int)K, (const bf16*)dy, (long)ldy, (const bf16*)x, (long)ldx, out, chunk,
+                     (int)options().dw_xcd, (float*)nullptr);
+  SNV_LAUNCH_CHECK();
+  evlog_end(s, EV_TRAIN, 2.0 * M * (double)N * K);
+  return 0;
+}
+
+static int launch_dw_det(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x, int64_t ldx,
+                         const DwOut& out, int splits, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (M == 0) return 0;
+  SNV_CHECK_ARG(ws && ((uintptr_t)ws % 16) == 0, "workspace: null or not 16-byte aligned");
+  SNV_CHECK_ARG(ws_bytes >= snvrag_linear_dw_det_ws_bytes(M, N, K, splits),
+                "workspace smaller than snvrag_linear_dw_det_ws_bytes()");
+  bool has_b = out.b[0] != nullptr;
+  for (int i = 0; i < 4; ++i) {
+    SNV_CHECK_ARG(((uintptr_t)out.w[i] % 16) == 0 && ((uintptr_t)out.b[i] % 16) == 0,
+                  "dw / db must be 16-byte aligned");
+    SNV_CHECK_ARG(!out.w[i] || (out.b[i] != nullptr) == has_b, "db: all parts or none");
+  }
+  int chunk, S;
+  dw_chunks(M, N, K, splits, chunk, S);
+  evlog_begin(s);
+  hipLaunchKernelGGL(dw_dma_kernel<true>, dim3((unsigned)((N / DW_T) * (K / DW_T) * S)), dim3(256), 0, s, (int)M,
+                     (int)N, (int)K, (const bf16*)dy, (long)ldy, (const bf16*)x, (long)ldx, out, chunk,
+                     (int)options().dw_xcd, (float*)ws);
+  SNV_LAUNCH_CHECK();
+  const long nk4 = N * K / 4, n4 = has_b ? N / 4 : 0;
+  hipLaunchKernelGGL(dw_reduce_kernel, dim3((unsigned)cdiv(nk4 + n4, 256)), dim3(256), 0, s, S, nk4, n4, (int)K,
+                     (const float*)ws, out);
   SNV_LAUNCH_CHECK();
   evlog_end(s, EV_TRAIN, 2.0 * M * (double)N * K);
   return 0;
@@ -251,19 +329,51 @@ extern "C" int snvrag_linear_dw(int64_t M, int64_t N, int64_t K, const void* dy,
   return launch_dw(M, N, K, dy, ldy, x, ldx, out, splits, as_stream(stream));
 }
 
-extern "C" int snvrag_linear_dw_parts(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x,
-                                      int64_t ldx, int n_parts, float* const* dw_parts, float* const* db_parts,
-                                      int splits, void* stream) {
-  if (int rc = dw_check(M, N, K, dy, ldy, x, ldx)) return rc;
+static int dw_parts_out(DwOut& out, int64_t N, int n_parts, float* const* dw_parts, float* const* db_parts) {
   SNV_CHECK_ARG(n_parts >= 1 && n_parts <= 4 && N % n_parts == 0 && (N / n_parts) % DW_T == 0,
                 "1-4 equal parts of N, each a multiple of 128");
   SNV_CHECK_ARG(dw_parts, "null pointer");
-  DwOut out{{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}, (int)(N / n_parts)};
+  out = DwOut{{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}, (int)(N / n_parts)};
   for (int i = 0; i < n_parts; ++i) {
     SNV_CHECK_ARG(dw_parts[i], "null dW part");
     out.w[i] = dw_parts[i];
     out.b[i] = db_parts ? db_parts[i] : nullptr;
     SNV_CHECK_ARG(!db_parts || db_parts[i], "null db part");
   }
+  return 0;
+}
+
+extern "C" int snvrag_linear_dw_parts(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x,
+                                      int64_t ldx, int n_parts, float* const* dw_parts, float* const* db_parts,
+                                      int splits, void* stream) {
+  if (int rc = dw_check(M, N, K, dy, ldy, x, ldx)) return rc;
+  DwOut out;
+  if (int rc = dw_parts_out(out, N, n_parts, dw_parts, db_parts)) return rc;
   return launch_dw(M, N, K, dy, ldy, x, ldx, out, splits, as_stream(stream));
+}
+
+extern "C" size_t snvrag_linear_dw_det_ws_bytes(int64_t M, int64_t N, int64_t K, int splits) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  int chunk, S;
+  dw_chunks(M, N, K, splits, chunk, S);
+  return (size_t)S * (size_t)(N * K + N) * sizeof(float);
+}
+
+extern "C" int snvrag_linear_dw_det(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x,
+                                    int64_t ldx, float* dw, float* db, int splits, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  if (int rc = dw_check(M, N, K, dy, ldy, x, ldx)) return rc;
+  SNV_CHECK_ARG(dw, "null pointer");
+  DwOut out{{dw, nullptr, nullptr, nullptr}, {db, nullptr, nullptr, nullptr}, (int)N};
+  return launch_dw_det(M, N, K, dy, ldy, x, ldx, out, splits, ws, ws_bytes, as_stream(stream));
+}
+
+extern "C" int snvrag_linear_dw_parts_det(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy,
+                                          const void* x, int64_t ldx, int n_parts, float* const* dw_parts,
+                                          float* const* db_parts, int splits, void* ws, size_t ws_bytes,
+                                          void* stream) {
+  if (int rc = dw_check(M, N, K, dy, ldy, x, ldx)) return rc;
+  DwOut out;
+  if (int rc = dw_parts_out(out, N, n_parts, dw_parts, db_parts)) return rc;
+  return launch_dw_det(M, N, K, dy, ldy, x, ldx, out, splits, ws, ws_bytes, as_stream(stream));
 }

@@ -22,6 +22,10 @@
 
 namespace snvrag {
 
+// DET (the deterministic training mode): ``loss_sum`` is the per-block partial array instead, block b
+// writes the sum of its 256 rows to loss_sum[b] (wave butterfly, then the four wave partials left to
+// right) and focal_final_kernel adds the partials in block order.
+template <bool DET>
 __global__ __launch_bounds__(256) void focal_kernel(long M, int C, const float* __restrict__ probs,
                                                     const int64_t* __restrict__ labels,
                                                     const uint8_t* __restrict__ mask, float gamma, float weight,
@@ -52,7 +56,28 @@ __global__ __launch_bounds__(256) void focal_kernel(long M, int C, const float* 
   l = wave_sum(l);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = l;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss_sum, red[0] + red[1] + red[2] + red[3]);
+  if (threadIdx.x == 0) {
+    if constexpr (DET) loss_sum[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    else atomicAdd(loss_sum, red[0] + red[1] + red[2] + red[3]);
+  }
+}
+
+// *loss_sum += part[0] + part[1] + ... + part[nb - 1], added one after the other in index order by
+// one thread (the partials staged through LDS 1024 at a time so the loads are coalesced and off the
+// dependent chain): nb = M / 256 is 194 at the training shape.
+__global__ __launch_bounds__(256) void focal_final_kernel(int nb, const float* __restrict__ part,
+                                                          float* __restrict__ loss_sum) {
+  __shared__ float buf[1024];
+  float s = 0.f;
+  for (int base = 0; base < nb; base += 1024) {
+    const int n = min(1024, nb - base);
+    for (int i = threadIdx.x; i < n; i += 256) buf[i] = part[base + i];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int i = 0; i < n; ++i) s += buf[i];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss_sum += s;
 }
 
 // Two passes with a fixed summation order (no float atomics): every rank of a data-parallel
@@ -156,8 +181,27 @@ extern "C" int snvrag_focal_loss(int64_t M, int C, const float* probs, const int
   SNV_CHECK_ARG(probs && labels && mask && loss_sum && grad, "null pointer");
   SNV_CHECK_ARG(C >= 1 && C <= 4, "classes must be 1..4");
   if (M == 0) return 0;
-  hipLaunchKernelGGL(focal_kernel, dim3(cdiv(M, 256)), dim3(256), 0, as_stream(stream), (long)M, C, probs, labels,
-                     mask, gamma, weight, loss_sum, grad);
+  hipLaunchKernelGGL(focal_kernel<false>, dim3(cdiv(M, 256)), dim3(256), 0, as_stream(stream), (long)M, C, probs,
+                     labels, mask, gamma, weight, loss_sum, grad);
+  SNV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t snvrag_focal_loss_det_ws_bytes(int64_t M) { return (size_t)cdiv(M, 256) * sizeof(float); }
+
+extern "C" int snvrag_focal_loss_det(int64_t M, int C, const float* probs, const int64_t* labels, const uint8_t* mask,
+                                     float gamma, float weight, float* loss_sum, float* grad, float* ws,
+                                     size_t ws_bytes, void* stream) {
+  SNV_CHECK_ARG(probs && labels && mask && loss_sum && grad, "null pointer");
+  SNV_CHECK_ARG(C >= 1 && C <= 4, "classes must be 1..4");
+  if (M == 0) return 0;
+  SNV_CHECK_ARG(ws && ws_bytes >= snvrag_focal_loss_det_ws_bytes(M),
+                "workspace smaller than snvrag_focal_loss_det_ws_bytes()");
+  const int nb = cdiv(M, 256);
+  hipLaunchKernelGGL(focal_kernel<true>, dim3(nb), dim3(256), 0, as_stream(stream), (long)M, C, probs, labels, mask,
+                     gamma, weight, ws, grad);
+  SNV_LAUNCH_CHECK();
+  hipLaunchKernelGGL(focal_final_kernel, dim3(1), dim3(256), 0, as_stream(stream), nb, (const float*)ws, loss_sum);
   SNV_LAUNCH_CHECK();
   return 0;
 }
@@ -848,6 +892,11 @@ __global__ __launch_bounds__(256) void nbr_mean_drop_fwd_kernel(NbrArgs a, float
 // by one thread (accumulated in place), dW rows get one atomic per (block, token row, feature).
 // (r3: 4 positions per 256-thread block, each thread 3 pairs in series: 258 blocks = one wave per
 // SIMD on a latency-bound loop, 0.50 ms per step at B = 24.)
+// DET (the deterministic training mode): every (token row, feature) of the LDS partial is touched by
+// exactly one thread of the block, so the LDS adds are plain, and the block stores its whole [V][D]
+// partial to dW[l] of a [L][V][D] workspace (zeros included); colsum_f32_kernel then adds the L
+// partials into the table gradient in its fixed order.
+template <bool DET>
 __global__ __launch_bounds__(256) void nbr_mean_drop_bwd_kernel(NbrArgs a, const float* __restrict__ dout,
                                                                 float* __restrict__ dW, float* __restrict__ dAr) {
   extern __shared__ float wacc[];                    // [V][D] block partials of dW
@@ -888,24 +937,33 @@ __global__ __launch_bounds__(256) void nbr_mean_drop_bwd_kernel(NbrArgs a, const
       }
       dAr[(long)l * a.D + d] += ar0;
       dAr[(long)l * a.D + d + 1] += ar1;
+      auto add = [&](int i, float v) {
+        if constexpr (DET) wacc[i] += v;
+        else atomicAdd(&wacc[i], v);
+      };
       if (site) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-          atomicAdd(&wacc[(a.tok0 + c) * a.D + d], w0[c]);
-          atomicAdd(&wacc[(a.tok0 + c) * a.D + d + 1], w1[c]);
+          add((a.tok0 + c) * a.D + d, w0[c]);
+          add((a.tok0 + c) * a.D + d + 1, w1[c]);
         }
       } else {
         const int t = l == 0 ? a.sos : (l == a.n_sites + 1 ? a.eos : a.pad);
         if (t != a.pad) {                              // nn.Embedding(padding_idx = <pad>): no gradient
-          atomicAdd(&wacc[t * a.D + d], ws0);
-          atomicAdd(&wacc[t * a.D + d + 1], ws1);
+          add(t * a.D + d, ws0);
+          add(t * a.D + d + 1, ws1);
         }
       }
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < a.V * a.D; i += blockDim.x)
-    if (wacc[i] != 0.f) unsafeAtomicAdd(dW + i, wacc[i]);
+  if constexpr (DET) {
+    float* __restrict__ part = dW + (long)blockIdx.x * a.V * a.D;
+    for (int i = threadIdx.x; i < a.V * a.D; i += blockDim.x) part[i] = wacc[i];
+  } else {
+    for (int i = threadIdx.x; i < a.V * a.D; i += blockDim.x)
+      if (wacc[i] != 0.f) unsafeAtomicAdd(dW + i, wacc[i]);
+  }
 }
 
 // ---- the hap head's last Linear(4D, 2) (foundation_model.py:25-33 net[2]) under autograd: bf16
@@ -1251,8 +1309,35 @@ extern "C" int snvrag_nbr_mean_drop_bwd(int64_t nq, int k, int64_t L, int D, int
   SNV_CHECK_ARG(dout && dW && dAr, "null pointer");
   if (nq == 0) return 0;
   const int nthr = (int)std::min<long>(256, (D / 2 + 63) / 64 * 64);
-  hipLaunchKernelGGL(nbr_mean_drop_bwd_kernel, dim3((unsigned)L), dim3(nthr), (size_t)V * D * sizeof(float),
+  hipLaunchKernelGGL(nbr_mean_drop_bwd_kernel<false>, dim3((unsigned)L), dim3(nthr), (size_t)V * D * sizeof(float),
                      as_stream(stream), a, dout, dW, dAr);
+  SNV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t snvrag_nbr_mean_drop_bwd_det_ws_bytes(int64_t L, int V, int D) {
+  return (size_t)std::max<int64_t>(L, 0) * (size_t)V * (size_t)D * sizeof(float);
+}
+
+extern "C" int snvrag_nbr_mean_drop_bwd_det(int64_t nq, int k, int64_t L, int D, int n_sites, int64_t ld_codes, int V,
+                                            const int32_t* inv, const uint8_t* codes, const float* W, const float* pe,
+                                            const float* Ar, float p, uint64_t seed, int tok0, int sos, int eos,
+                                            int pad, const float* dout, float* dW, float* dAr, void* ws,
+                                            size_t ws_bytes, void* stream) {
+  NbrArgs a;
+  if (int rc = nbr_args(a, nq, k, L, D, n_sites, ld_codes, V, inv, codes, W, pe, Ar, p, seed, tok0, sos, eos, pad))
+    return rc;
+  SNV_CHECK_ARG(dout && dW && dAr, "null pointer");
+  if (nq == 0) return 0;
+  SNV_CHECK_ARG(ws && ws_bytes >= snvrag_nbr_mean_drop_bwd_det_ws_bytes(L, V, D),
+                "workspace smaller than snvrag_nbr_mean_drop_bwd_det_ws_bytes()");
+  const int nthr = (int)std::min<long>(256, (D / 2 + 63) / 64 * 64);
+  hipLaunchKernelGGL(nbr_mean_drop_bwd_kernel<true>, dim3((unsigned)L), dim3(nthr), (size_t)V * D * sizeof(float),
+                     as_stream(stream), a, dout, (float*)ws, dAr);
+  SNV_LAUNCH_CHECK();
+  // dW[i] += the L partials of element i, summed in colsum_f32_kernel's fixed order
+  hipLaunchKernelGGL(colsum_f32_kernel, dim3(cdiv((long)V * D, 16)), dim3(256), 0, as_stream(stream), (long)L, V * D,
+                     (const float*)ws, dW, 1);
   SNV_LAUNCH_CHECK();
   return 0;
 }

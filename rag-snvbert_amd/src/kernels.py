@@ -502,6 +502,28 @@ def option(name: str, value: int):
         set_option(name, prev)
 
 
+# --------------------------------------------------- deterministic mode --
+# Library option ``deterministic`` (default 0): linear_dw, linear_dw_parts, nbr_mean_drop_bwd and
+# focal_loss call the fixed-order ``*_det`` entry points, whose partials go to one cached
+# workspace per (device, stream) — launches of one stream run one after the other and reuse it, two
+# streams never share one.  With the option off nothing here is touched.
+_det_ws: dict = {}
+
+
+def deterministic() -> bool:
+    v = C.c_int64()
+    check(N.lib().snvrag_get_option(b"deterministic", C.byref(v)), "get_option")
+    return bool(v.value)
+
+
+def _det_workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream_ptr())
+    ws = _det_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _det_ws[key] = torch.empty(max(int(nbytes), 16), device=dev, dtype=torch.uint8)
+    return ws
+
+
 # ---------------------------------------------------------------- training --
 def attention_train_fwd(qkv: torch.Tensor, nseq: int, L: int, heads: int, dh: int, dropout_p: float = 0.0,
                         seed: int = 0):
@@ -544,6 +566,13 @@ def focal_loss(probs: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor, ga
     if loss_acc is None:
         loss_acc = torch.zeros(1, device=probs.device, dtype=torch.float32)
     grad = torch.empty_like(p)
+    if deterministic():
+        nb = int(N.lib().snvrag_focal_loss_det_ws_bytes(M))
+        ws = _det_workspace(p.device, nb)
+        check(N.lib().snvrag_focal_loss_det(M, Cc, ptr(p), ptr(lab), ptr(msk), float(gamma), float(weight),
+                                            ptr(loss_acc), ptr(grad), ptr(ws), ws.numel(), stream_ptr()),
+              "focal_loss_det")
+        return loss_acc, grad
     check(N.lib().snvrag_focal_loss(M, Cc, ptr(p), ptr(lab), ptr(msk), float(gamma), float(weight), ptr(loss_acc),
                                     ptr(grad), stream_ptr()), "focal_loss")
     return loss_acc, grad
@@ -669,6 +698,15 @@ def nbr_mean_drop_bwd(dout: torch.Tensor, inv: torch.Tensor, codes: torch.Tensor
     nq, k = inv.shape
     L, D = pe.shape
     assert dW.dtype == dAr.dtype == torch.float32 and dW.is_contiguous() and dAr.is_contiguous()
+    if deterministic():
+        nb = int(N.lib().snvrag_nbr_mean_drop_bwd_det_ws_bytes(L, W.shape[0], D))
+        ws = _det_workspace(dW.device, nb)
+        check(N.lib().snvrag_nbr_mean_drop_bwd_det(nq, k, L, D, n_sites, codes.shape[1], W.shape[0], ptr(_c(inv)),
+                                                   ptr(_c(codes)), ptr(_c(W)), ptr(_c(pe)), ptr(_c(Ar)), float(p),
+                                                   int(seed) & (2 ** 64 - 1), tok0, sos, eos, pad,
+                                                   ptr(_c(dout.float())), ptr(dW), ptr(dAr), ptr(ws), ws.numel(),
+                                                   stream_ptr()), "nbr_mean_drop_bwd_det")
+        return
     check(N.lib().snvrag_nbr_mean_drop_bwd(nq, k, L, D, n_sites, codes.shape[1], W.shape[0], ptr(_c(inv)),
                                            ptr(_c(codes)), ptr(_c(W)), ptr(_c(pe)), ptr(_c(Ar)), float(p),
                                            int(seed) & (2 ** 64 - 1), tok0, sos, eos, pad,
@@ -694,6 +732,12 @@ def linear_dw(dy: torch.Tensor, x: torch.Tensor, bias: bool = False, splits: int
         db = torch.zeros(Nn, device=dy.device, dtype=torch.float32)
     if db is not None:
         assert db.dtype == torch.float32 and db.is_contiguous() and db.numel() == Nn
+    if deterministic():
+        nb = int(N.lib().snvrag_linear_dw_det_ws_bytes(M, Nn, Kk, int(splits)))
+        ws = _det_workspace(dy.device, nb)
+        check(N.lib().snvrag_linear_dw_det(M, Nn, Kk, ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), ptr(db),
+                                           int(splits), ptr(ws), ws.numel(), stream_ptr()), "linear_dw_det")
+        return dw, db
     check(N.lib().snvrag_linear_dw(M, Nn, Kk, ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), ptr(db),
                                    int(splits), stream_ptr()), "linear_dw")
     return dw, db
@@ -717,6 +761,13 @@ def linear_dw_parts(dy: torch.Tensor, x: torch.Tensor, dws, dbs=None, splits: in
     import ctypes
     wp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in dws])
     bp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in dbs]) if dbs is not None else None
+    if deterministic():
+        nb = int(N.lib().snvrag_linear_dw_det_ws_bytes(M, Nn, Kk, int(splits)))
+        ws = _det_workspace(dy.device, nb)
+        check(N.lib().snvrag_linear_dw_parts_det(M, Nn, Kk, ptr(dy), dy.stride(0), ptr(x), x.stride(0), n, wp, bp,
+                                                 int(splits), ptr(ws), ws.numel(), stream_ptr()),
+              "linear_dw_parts_det")
+        return
     check(N.lib().snvrag_linear_dw_parts(M, Nn, Kk, ptr(dy), dy.stride(0), ptr(x), x.stride(0), n, wp, bp,
                                          int(splits), stream_ptr()), "linear_dw_parts")
 

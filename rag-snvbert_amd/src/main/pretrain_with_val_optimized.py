@@ -75,8 +75,13 @@ class BERTTrainerWithValidationOptimized:
                  with_cuda: bool = True, cuda_devices=None, log_freq: int = 10, grad_accum_steps: int = 1,
                  focal_gamma: float = 2.0, use_recon_loss: bool = False, patience: int = 5,
                  val_metric: str = "f1", min_delta: float = 0.001, rare_threshold: float = 0.05,
-                 output_csv: Optional[str] = None, max_grad_norm: float = 1.0, bucket_bytes: int = 32 << 20):
+                 output_csv: Optional[str] = None, max_grad_norm: float = 1.0, bucket_bytes: int = 32 << 20,
+                 deterministic: bool = False):
         self.use_recon_loss = bool(use_recon_loss)
+        # True: every train_step runs with the library option ``deterministic`` on (fixed-order weight
+        # gradient, token-table gradient and loss sums, src/kernels.py) — the same inputs, seeds and
+        # neighbours then give the same weights bit for bit.  No reference counterpart; off by default.
+        self.deterministic = bool(deterministic)
         self.device = next(model.parameters()).device
         self.model = model
         self.train_data, self.val_data, self.vocab = train_dataloader, val_dataloader, vocab
@@ -143,7 +148,15 @@ class BERTTrainerWithValidationOptimized:
 
     def train_step(self, data: Dict) -> torch.Tensor:
         """One micro-batch: retrieval, forward, loss, backward (+ optimizer step on the last
-        micro-batch of an accumulation group).  Returns the device loss (no sync)."""
+        micro-batch of an accumulation group).  Returns the device loss (no sync).
+        ``self.deterministic``: the whole step under the library's deterministic option."""
+        if not self.deterministic:
+            return self._train_step(data)
+        from .. import kernels
+        with kernels.option("deterministic", 1):
+            return self._train_step(data)
+
+    def _train_step(self, data: Dict) -> torch.Tensor:
         ds = self.rag_train_dataset
         # train mode BEFORE retrieval (pretrain_with_val_optimized.py:127): after validate() the
         # model is in eval mode, and retrieval in eval mode would return detached means

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("SNVRAG_LIB", PKG_DIR / "lib" / "libsnvrag.so"))
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 vp, i64, i32, f32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
 
@@ -185,6 +185,15 @@ _SIGS = {
     "snvrag_linear_dw": ([i64, i64, i64, vp, i64, vp, i64, vp, vp, C.c_int, vp], C.c_int),
     "snvrag_linear_dw_parts": ([i64, i64, i64, vp, i64, vp, i64, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, vp],
                                C.c_int),
+    "snvrag_linear_dw_det_ws_bytes": ([i64, i64, i64, C.c_int], sz),
+    "snvrag_linear_dw_det": ([i64, i64, i64, vp, i64, vp, i64, vp, vp, C.c_int, vp, sz, vp], C.c_int),
+    "snvrag_linear_dw_parts_det": ([i64, i64, i64, vp, i64, vp, i64, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int,
+                                    vp, sz, vp], C.c_int),
+    "snvrag_nbr_mean_drop_bwd_det_ws_bytes": ([i64, C.c_int, C.c_int], sz),
+    "snvrag_nbr_mean_drop_bwd_det": ([i64, C.c_int, i64, C.c_int, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, f32,
+                                      C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp], C.c_int),
+    "snvrag_focal_loss_det_ws_bytes": ([i64], sz),
+    "snvrag_focal_loss_det": ([i64, C.c_int, vp, vp, vp, f32, f32, vp, vp, vp, sz, vp], C.c_int),
     "snvrag_evlog_enable": ([C.c_int], C.c_int),
     "snvrag_evlog_pause": ([C.c_int], C.c_int),
     "snvrag_evlog_reset": ([], C.c_int),

@@ -4,7 +4,8 @@ Same command-line surface as the reference (dataset/panel/freq/window/type/pop/p
 model and optimiser hyper-parameters, rag_k, resume, output) plus:
   --synthetic N_SAMPLES   build the data in memory (src/dataset/synthetic.py) — this image
                           has no 1000-Genomes files and no h5py/allel to read them;
-  --max_steps N           stop an epoch after N batches (smoke runs).
+  --max_steps N           stop an epoch after N batches (smoke runs);
+  --deterministic         fixed-order reductions in the training step (two runs, one checkpoint).
 Multi-GPU: launch one process per GPU with torch.distributed.run; ranks walk the windows
 in lock-step (DistributedWindowSampler), sum gradients with bucketed RCCL all-reduces
 (src/main/optimizer.py: the reference's DataParallel gradient over the global batch), sum
@@ -65,7 +66,19 @@ def parse_args(argv=None):
     p.add_argument("--dist_backend", default="nccl", choices=["nccl", "gloo"],
                    help="process-group backend for WORLD_SIZE > 1: nccl (= RCCL, one GPU per rank) or "
                         "gloo (host-staged collectives: the multi-rank tests with all ranks on one GPU)")
+    p.add_argument("--deterministic", action="store_true",
+                   help="fixed-order reductions in every training step (no float atomics): two runs of the same "
+                        "command give the same checkpoint; no reference counterpart, off by default")
     return p.parse_args(argv)
+
+
+def trainer_kwargs(args, rank: int = 0) -> dict:
+    """The trainer's keyword arguments from the parsed command line."""
+    return dict(lr=args.lr, weight_decay=args.weight_decay, warmup_steps=args.warmup_steps, log_freq=args.log_freq,
+                grad_accum_steps=args.grad_accum_steps, focal_gamma=args.focal_gamma,
+                use_recon_loss=args.use_recon_loss.lower() == "true", patience=args.patience,
+                val_metric=args.val_metric, min_delta=args.min_delta, rare_threshold=args.rare_threshold,
+                output_csv=args.metrics_csv if rank == 0 else None, deterministic=args.deterministic)
 
 
 def build_data(args, rank: int, world: int):
@@ -136,12 +149,7 @@ def main(argv=None):
                 t.data.copy_(h)
             else:
                 dist.broadcast(t.data, 0)
-    trainer = BERTTrainerWithValidationOptimized(
-        model, train_loader, val_loader, vocab, lr=args.lr, weight_decay=args.weight_decay,
-        warmup_steps=args.warmup_steps, log_freq=args.log_freq, grad_accum_steps=args.grad_accum_steps,
-        focal_gamma=args.focal_gamma, use_recon_loss=args.use_recon_loss.lower() == "true",
-        patience=args.patience, val_metric=args.val_metric, min_delta=args.min_delta,
-        rare_threshold=args.rare_threshold, output_csv=args.metrics_csv if rank == 0 else None)
+    trainer = BERTTrainerWithValidationOptimized(model, train_loader, val_loader, vocab, **trainer_kwargs(args, rank))
     trainer.rag_k = args.rag_k
     start = 0
     if args.resume_path:
