@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SNVRAG_ABI_VERSION 29
+#define SNVRAG_ABI_VERSION 30
 
 enum { SNVRAG_F32 = 0, SNVRAG_BF16 = 1 };
 enum { SNVRAG_ACT_NONE = 0, SNVRAG_ACT_GELU = 1, SNVRAG_ACT_LRELU = 2, SNVRAG_ACT_SIGMOID = 3 };
@@ -271,6 +271,37 @@ int snvrag_rag_mean_counts(int dtype_out, int64_t nq, int64_t L, int64_t D, int 
                            const uint8_t* counts, int64_t ld_counts, int32_t n_sites,
                            const float* W, const float* pe, const float* Ar,
                            int tok0, int tok1, int sos, int eos, int pad, void* out, void* stream);
+
+/* Bit-packed panel index (opt-in; the u8 index above stays the default).  The same 0/1 alleles
+ * (the index that replaces embedding_rag_dataset.py:334-377 / embedding_rag_infer_dataset.py:71-224)
+ * at 1 bit per site: bits u8 [n_ref, ld_bits], ld_bits >= n_sites_pad / 8 with n_sites_pad a
+ * multiple of 256 (rows are 32-B multiples); site s of row r is bit (s & 7) of byte (s >> 3)
+ * (little-endian in the byte, numpy.packbits(bitorder="little")); padding sites are 0.
+ * snvrag_panel_pack_bits: u8 codes [n, ld] (bit 0 of each byte) -> bits [n, ld_bits].
+ * snvrag_panel_synth_bits: rows [row0, row0 + n_rows) of snvrag_panel_synth_rows' panel, as bits.
+ * snvrag_panel_unpack_rows: out u8 [n_rows, ld_out] = the 0/1 bytes of bit rows rows[i]; zero
+ *   rows for indices outside [0, n_ref) and zero past 8 * ld_bits sites (the gather the training
+ *   paths use for the unique retrieved rows: embedding_rag_dataset.py:404-442).
+ * snvrag_knn_scan_bits: snvrag_knn_scan over bit rows — same arguments, same part_keys, bit for
+ *   bit; n_sites_pad % 256 == 0 and <= 1280.  Each workgroup expands its stage of bit rows once
+ *   into the LDS stage of 0/1 bytes that the u8 scan fills by LDS-DMA.
+ * snvrag_rag_mean_bits / snvrag_neighbor_counts_bits: snvrag_rag_mean / snvrag_neighbor_counts
+ *   (bert.py:176-179 K-mean) reading the neighbours' bit rows in place; counts rows ld_out >= 8 * ld_bits. */
+int snvrag_panel_pack_bits(const uint8_t* codes, int64_t n, int64_t ld, uint8_t* bits, int64_t ld_bits,
+                           void* stream);
+int snvrag_panel_synth_bits(uint8_t* bits, int64_t row0, int64_t n_rows, int64_t ld_bits, int32_t n_sites,
+                            const float* af, uint64_t seed, void* stream);
+int snvrag_panel_unpack_rows(const uint8_t* bits, int64_t n_ref, int64_t ld_bits, const int64_t* rows,
+                             int64_t n_rows, uint8_t* out, int64_t ld_out, void* stream);
+int snvrag_knn_scan_bits(const uint8_t* bits, int64_t n_ref, int64_t ld_bits, int32_t n_sites_pad,
+                         const void* lut, int32_t nq, int limbs, int k, int64_t ref_offset,
+                         uint64_t* part_keys, int32_t n_parts, const int32_t* th_init, void* stream);
+int snvrag_rag_mean_bits(int dtype_out, int64_t nq, int64_t L, int64_t D, int k, const int64_t* idx,
+                         const uint8_t* bits, int64_t ld_bits, int32_t n_sites,
+                         const float* W, const float* pe, const float* Ar,
+                         int tok0, int tok1, int sos, int eos, int pad, void* out, void* stream);
+int snvrag_neighbor_counts_bits(int64_t nq, int k, const int64_t* idx, const uint8_t* bits, int64_t ld_bits,
+                                int64_t row0, int64_t n_rows, uint8_t* counts, int64_t ld_out, void* stream);
 
 /* Raw-genotype window index (build_ref_db_l2.py:15-98: faiss.IndexFlatL2 over each
  * sample's flattened (window_len, 2) 0/1 genotypes; test_faiss_intersect.py:171-181 the

@@ -16,6 +16,12 @@
 //                   VGPRs (no reuse to stage), exact per-range top-k kept in LDS
 //                   with a strict-threshold filter + wave bitonic compaction.
 //   merge_kernel  : hierarchical LDS bitonic merge of the per-range lists.
+//
+// Bit-packed panel (opt-in): bits u8 [N][n_sites_pad / 8], site s of a row = bit
+// s & 7 of byte s >> 3 (numpy.packbits(bitorder="little")), padding sites 0.  scan2_kernel's BITS
+// form expands each stage of bit rows once per workgroup into the u8 form's LDS stage;
+// rag_mean_kernel / neighbor_counts_kernel read the neighbours' bit rows in place;
+// panel_pack_bits / panel_synth_bits / panel_unpack_rows build the index and gather u8 rows.
 #include "common.h"
 
 namespace snvrag {
@@ -483,7 +489,8 @@ constexpr int RM_P = 8, RM_Q = 16, RM_KMAX = 128;
 // CNT: `codes` holds per-query alt-allele counts over the k neighbours ([nq][ld], the
 // sharded-panel form, see neighbor_counts_kernel) instead of panel rows indexed by idx;
 // idx still gives the number of valid neighbours.
-template <typename T, bool CNT = false>
+// BITS: `codes` is the bit-packed panel (ld = row bytes): the k neighbours' bits are read in place.
+template <typename T, bool CNT = false, bool BITS = false>
 __global__ __launch_bounds__(256) void rag_mean_kernel(int nq, int L, int D, int k, const int64_t* __restrict__ idx,
                                                        const uint8_t* __restrict__ codes, long ld, int n_sites,
                                                        const float* __restrict__ W, const float* __restrict__ pe,
@@ -506,7 +513,8 @@ __global__ __launch_bounds__(256) void rag_mean_kernel(int nq, int L, int D, int
     for (int j = 0; j < k; ++j) {
       const int64_t r = sidx[qq * k + j];
       nv += r >= 0;
-      if constexpr (!CNT) c += (r >= 0 && site) ? codes[r * ld + (l - 1)] : 0;
+      if constexpr (BITS) c += (r >= 0 && site) ? (codes[r * ld + ((l - 1) >> 3)] >> ((l - 1) & 7)) & 1 : 0;
+      else if constexpr (!CNT) c += (r >= 0 && site) ? codes[r * ld + (l - 1)] : 0;
     }
     if constexpr (CNT) c = (site && q0 + qq < nq) ? codes[(long)(q0 + qq) * ld + (l - 1)] : 0;
     frac[qq][p] = nv > 0 ? (float)c / (float)nv : 0.f;
@@ -549,6 +557,15 @@ __global__ __launch_bounds__(256) void rag_mean_kernel(int nq, int L, int D, int
 }
 
 // ---------------------------------------------------------- panel synth ---
+// 16 panel bits (site s = bit s) -> 16 bytes of 0/1: per nibble n, (n * 0x00204081) & 0x01010101
+// puts bit e of n into byte e (the four shifted copies of n do not overlap, so nothing carries)
+__device__ __forceinline__ u32x4 expand16(uint32_t w) {
+  u32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = (((w >> (4 * e)) & 0xFu) * 0x00204081u) & 0x01010101u;
+  return o;
+}
+
 __device__ __forceinline__ double hash_u01(uint64_t seed, uint64_t r, uint64_t c) {
   uint64_t x = seed * 0x9E3779B97F4A7C15ull + r * 0xD1B54A32D192ED03ull + c * 0x8CB92BA72F3D8DD7ull;
   x += 0x9E3779B97F4A7C15ull;
@@ -562,6 +579,8 @@ __device__ __forceinline__ double hash_u01(uint64_t seed, uint64_t r, uint64_t c
 // codes[idx[q][j] - row0][s] for the idx[q][j] in [row0, row0 + n_rows) (global indices).
 // One thread per (query, 16-site chunk); the shards' partial counts sum (all-reduce) to the
 // full count, which rag_mean_kernel<T, true> turns into the neighbour mean.
+// BITS: the shard is bit-packed (ld = row bytes, ld * 8 sites): 16 sites = 2 bytes per neighbour row.
+template <bool BITS>
 __global__ __launch_bounds__(256) void neighbor_counts_kernel(int nq, int k, const int64_t* __restrict__ idx,
                                                               const uint8_t* __restrict__ codes, long ld,
                                                               long row0, long n_rows, uint8_t* __restrict__ counts,
@@ -574,8 +593,10 @@ __global__ __launch_bounds__(256) void neighbor_counts_kernel(int nq, int k, con
   uint32_t acc[4] = {0, 0, 0, 0};                    // 16 byte counters (k <= 128: no carries)
   for (int j = 0; j < k; ++j) {
     const long r = idx[(long)q * k + j] - row0;
-    if (r < 0 || r >= n_rows || c0 >= ld) continue;
-    const u32x4 v = *reinterpret_cast<const u32x4*>(codes + r * ld + c0);
+    if (r < 0 || r >= n_rows || c0 >= (BITS ? 8 * ld : ld)) continue;
+    u32x4 v;
+    if constexpr (BITS) v = expand16(*reinterpret_cast<const uint16_t*>(codes + r * ld + c0 / 8));
+    else v = *reinterpret_cast<const u32x4*>(codes + r * ld + c0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i] += v[i];      // codes are 0/1 bytes: packed byte adds
   }
@@ -597,6 +618,57 @@ __global__ void panel_synth_kernel(uint8_t* __restrict__ codes, long n_ref, long
     }
     *reinterpret_cast<u32x4*>(codes + r * ld + c0) = *reinterpret_cast<u32x4*>(v);
   }
+}
+
+// The same panel straight as bits: one thread per (row, 16 sites) writes two bytes.
+__global__ void panel_synth_bits_kernel(uint8_t* __restrict__ bits, long n_ref, long ldb, int n_sites,
+                                        const float* __restrict__ af, uint64_t seed, long row0) {
+  const long chunks_per_row = ldb / 2;
+  const long total = n_ref * chunks_per_row;
+  for (long id = (long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long)gridDim.x * blockDim.x) {
+    const long r = id / chunks_per_row;
+    const int c0 = (int)(id % chunks_per_row) * 16;
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int s = c0 + j;
+      w |= (uint32_t)(s < n_sites && hash_u01(seed, (uint64_t)(r + row0), (uint64_t)s) < (double)af[s]) << j;
+    }
+    *reinterpret_cast<uint16_t*>(bits + r * ldb + c0 / 8) = (uint16_t)w;
+  }
+}
+
+// u8 codes [n, ld] -> bits [n, ldb]: one thread per (row, 16 sites); sites past ld are 0
+__global__ void panel_pack_bits_kernel(const uint8_t* __restrict__ codes, long n, long ld, uint8_t* __restrict__ bits,
+                                       long ldb) {
+  const long chunks_per_row = ldb / 2;
+  const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= n * chunks_per_row) return;
+  const long r = id / chunks_per_row;
+  const long c0 = (id % chunks_per_row) * 16;
+  uint32_t w = 0;
+  if (c0 < ld) {                                     // ld is a multiple of 16: the chunk is whole
+    const u32x4 v = *reinterpret_cast<const u32x4*>(codes + r * ld + c0);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w |= ((v[j >> 2] >> (8 * (j & 3))) & 1u) << j;
+  }
+  *reinterpret_cast<uint16_t*>(bits + r * ldb + c0 / 8) = (uint16_t)w;
+}
+
+// bits + row list -> u8 rows [n_rows, ld_out]: one thread per (output row, 16 sites); a row index
+// outside [0, n_ref) and sites past the bit row give zeros
+__global__ void panel_unpack_rows_kernel(const uint8_t* __restrict__ bits, long n_ref, long ldb,
+                                         const int64_t* __restrict__ rows, long n_rows, uint8_t* __restrict__ out,
+                                         long ld_out) {
+  const long chunks_per_row = ld_out / 16;
+  const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= n_rows * chunks_per_row) return;
+  const long i = id / chunks_per_row;
+  const long c0 = (id % chunks_per_row) * 16;
+  const long r = rows[i];
+  u32x4 v = u32x4{0, 0, 0, 0};
+  if (r >= 0 && r < n_ref && c0 < 8 * ldb) v = expand16(*reinterpret_cast<const uint16_t*>(bits + r * ldb + c0 / 8));
+  *reinterpret_cast<u32x4*>(out + i * ld_out + c0) = v;
 }
 
 // ------------------------------------------------------------ scan v2 ---
@@ -635,6 +707,8 @@ __device__ __forceinline__ void vm_wait_stages(int y) {
     vm_wait_stages<PPW, V - 1>(y);
   }
 }
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+constexpr int S2B_PD = 3;                 // bit form: stages of bits in flight in VGPRs (2 VGPRs each)
 #ifndef S2_QTW1
 #define S2_QTW1 1                         // query tiles per wave of the reduced one-limb scan
 #endif
@@ -656,7 +730,13 @@ __device__ __forceinline__ void compact_row2(uint64_t* buf, int row, int cnt, in
 //                       fragment read from LDS feeds two MFMAs — half the LDS read traffic
 //                       of the 2-limb shape, whose 8 waves x 32 KiB per stage saturate
 //                       the 128 B/clk LDS port.  Waves 4..7 only stream codes.
-template <int KS, int LIMBS, int QTW, int MODE>
+//
+// BITS: `codes` is the bit-packed panel (bits[n_ref][ld], ld = row bytes = n_sites_pad / 8, site s
+// of a row = bit s & 7 of byte s >> 3).  The stage fill is then HBM -> VGPR (8 B = one row's 64
+// sites of one k-step per thread, S2B_PD stages in flight) -> nibble-to-dword expansion -> ds_write
+// of the SAME swizzled 0/1-byte stage the u8 form fills by LDS-DMA, once per workgroup; the B
+// fragment reads, MFMAs, filter and compaction below are shared, so the keys are identical.
+template <int KS, int LIMBS, int QTW, int MODE, bool BITS = false>
 __device__ __forceinline__ void scan2_body(char* smem, const uint8_t* __restrict__ codes, long n_ref, long ld,
                                            const int8_t* __restrict__ lut, const int* __restrict__ mult, int nq,
                                            int k, long range, long ref_offset, uint64_t* __restrict__ parts,
@@ -665,7 +745,7 @@ __device__ __forceinline__ void scan2_body(char* smem, const uint8_t* __restrict
   constexpr int S2_R = s2_rows(KS);
   constexpr int STAGE = S2_R * ROWB;
   constexpr int PPW = STAGE / 1024 / 8;                // glds pieces per wave per stage
-  constexpr int NST = s2_nst(KS);                      // ring depth
+  constexpr int NST = BITS ? 2 : s2_nst(KS);           // ring depth (bits: double buffer)
   static_assert(NST >= 2, "stage too large");
   static_assert(PPW * (NST - 2) <= 63, "vmcnt range");
   static_assert(ROWB % 256 == 0 && PPW >= 1, "rows must be multiples of 256 B");
@@ -730,93 +810,76 @@ __device__ __forceinline__ void scan2_body(char* smem, const uint8_t* __restrict
     asm volatile("" ::"v"(th[t][0]), "v"(th[t][1]), "v"(th[t][2]), "v"(th[t][3]), "v"(mul[t][0]), "v"(mul[t][1]),
                  "v"(mul[t][2]), "v"(mul[t][3]));
 
+  if constexpr (!BITS) {
 #pragma unroll
-  for (int j = 0; j < NST - 1; ++j)
-    if (j < nstage) issue(j, r_begin + (long)j * S2_R);
-  for (int it = 0; it < nstage; ++it) {
-    // retire stage it; up to NST-2 younger stages stay in flight across the barrier
-    vm_wait_stages<PPW, NST - 2>(nstage - 1 - it);
-    __builtin_amdgcn_s_barrier();
-    if (MODE != 2 && it + NST - 1 < nstage) issue((it + NST - 1) % NST, r_begin + (long)(it + NST - 1) * S2_R);
-    if (!active || MODE == 1) continue;
-    const char* st = smem + (it % NST) * STAGE;
-    const long r0 = r_begin + (long)it * S2_R;
-    // B fragments (16 haplotypes x 64 sites) of both 16-row groups as one stream,
-    // read PF ahead of their MFMAs so LDS latency hides under the MFMA chain
-    constexpr int RG = S2_R / 16, F = RG * KS, PF = 4;
-    auto bfrag = [&](int f) {
-      const int row = 16 * (f / KS) + li, ks = f % KS;
-      return *reinterpret_cast<const i32x4*>(st + row * ROWB + (((4 * ks + lg) ^ (row & 15)) << 4));
+    for (int j = 0; j < NST - 1; ++j)
+      if (j < nstage) issue(j, r_begin + (long)j * S2_R);
+    for (int it = 0; it < nstage; ++it) {
+      // retire stage it; up to NST-2 younger stages stay in flight across the barrier
+      vm_wait_stages<PPW, NST - 2>(nstage - 1 - it);
+      __builtin_amdgcn_s_barrier();
+      if (MODE != 2 && it + NST - 1 < nstage) issue((it + NST - 1) % NST, r_begin + (long)(it + NST - 1) * S2_R);
+      if (!active || MODE == 1) continue;
+#include "knn_scan2_stage.h"
+    }
+  } else {
+    // Unit u = (row u / KS, k-step u % KS) of a stage: 8 bytes of bits, consecutive threads read
+    // consecutive bytes of a row.  Stage s lives in register slot s % S2B_PD from its load until
+    // its expansion S2B_PD iterations later; the loads are plain ones, so hipcc counts them
+    // (vmcnt leaves the younger slots in flight).  Per iteration: barrier (stage `it` is complete
+    // in buffer it & 1, every wave has finished stage it - 1 in the other one), expand stage
+    // it + 1 into that other buffer, refill its slot, compute stage `it`.
+    constexpr int NU = (S2_R * KS + 511) / 512;
+    u32x2 pre[S2B_PD][NU];
+    auto bload = [&](u32x2(&v)[NU], int sidx) __attribute__((always_inline)) {
+      const long r0 = r_begin + (long)sidx * S2_R;
+#pragma unroll
+      for (int j = 0; j < NU; ++j) {
+        const int u = tid + 512 * j;
+        if (u < S2_R * KS) {
+          long r = r0 + u / KS;
+          r = r < r_end ? r : r_end - 1;
+          v[j] = *reinterpret_cast<const u32x2*>(codes + r * ld + (u % KS) * 8);
+        }
+      }
     };
-    i32x4 bq[PF];
+    auto bexpand = [&](const u32x2(&v)[NU], int sidx) __attribute__((always_inline)) {
+      char* st = smem + (sidx % NST) * STAGE;
 #pragma unroll
-    for (int f = 0; f < PF; ++f) bq[f] = bfrag(f);
-    i32x4 acc[RG][QTW][LIMBS];
+      for (int j = 0; j < NU; ++j) {
+        const int u = tid + 512 * j;
+        if (u < S2_R * KS) {
+          const int row = u / KS, ks = u % KS;
 #pragma unroll
-    for (int rg = 0; rg < RG; ++rg)
-#pragma unroll
-      for (int t = 0; t < QTW; ++t)
-#pragma unroll
-        for (int lb = 0; lb < LIMBS; ++lb) acc[rg][t][lb] = i32x4{0, 0, 0, 0};
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-      const i32x4 b = bq[f % PF];
-      if (f + PF < F) bq[f % PF] = bfrag(f + PF);
-#pragma unroll
-      for (int t = 0; t < QTW; ++t)
-#pragma unroll
-        for (int lb = 0; lb < LIMBS; ++lb)
-          acc[f / KS][t][lb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[lb][t][f % KS], b, acc[f / KS][t][lb], 0, 0, 0);
-    }
-    // pin the interleave (hipcc otherwise sinks each read to just before its MFMA):
-    // PF reads, then per fragment {1 read, QTW*LIMBS MFMAs}
-    __builtin_amdgcn_sched_group_barrier(0x100, PF, 0);
-#pragma unroll
-    for (int f = 0; f < F; ++f) {
-      if (f + PF < F) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, QTW * LIMBS, 0);
-    }
-#pragma unroll
-    for (int rg = 0; rg < RG; ++rg) {
-      const long r = r0 + 16 * rg + li;
-      const bool rv = r < r_end;
-#pragma unroll
-      for (int t = 0; t < QTW; ++t) {
-        uint64_t* buf = cand + (wave * QTW + t) * 16 * S2_CAP;
-        int dd[4];
-        bool anyp = false;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          dd[i] = LIMBS == 2 ? acc[rg][t][0][i] * 128 + acc[rg][t][1][i] : acc[rg][t][0][i] * mul[t][i];
-          anyp |= dd[i] < th[t][i];
-        }
-        if (!__ballot(rv && anyp)) continue;   // the common case once the threshold is tight
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int d = dd[i];
-          const bool pass = rv && d < th[t][i];
-          const uint64_t m = __ballot(pass);
-          if (m) {
-            const uint32_t gb = (uint32_t)(m >> (16 * lg)) & 0xFFFFu;
-            if (pass) {
-              const int pre = __popc(gb & ((1u << li) - 1u));
-              buf[(4 * lg + i) * S2_CAP + cnt[t][i] + pre] = make_key(d, (uint32_t)(r + ref_offset));
-            }
-            cnt[t][i] += __popc(gb);
+          for (int h = 0; h < 4; ++h) {                  // 16 sites -> one 16-B chunk of 0/1 bytes
+            const uint32_t w = (h < 2 ? v[j][0] : v[j][1]) >> (16 * (h & 1));
+            *reinterpret_cast<u32x4*>(st + row * ROWB + (((4 * ks + h) ^ (row & 15)) << 4)) = expand16(w);
           }
         }
+      }
+    };
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          uint64_t need = __ballot(cnt[t][i] > S2_TH);
-          while (need) {
-            const int src = __builtin_ctzll(need);
-            const int g = src >> 4;
-            need &= ~(0xFFFFull << (16 * g));
-            int nc, nt;
-            compact_row2(buf, 4 * g + i, __shfl(cnt[t][i], src, 64), k, lane, nc, nt);
-            if (lg == g) { cnt[t][i] = nc; th[t][i] = nt; }
-          }
+    for (int p = 0; p < S2B_PD; ++p)
+      if (p < nstage) bload(pre[p], p);
+    if (nstage > 0) {
+      bexpand(pre[0], 0);
+      if (S2B_PD < nstage) bload(pre[0], S2B_PD);
+    }
+    for (int base = 0; base < nstage; base += S2B_PD) {
+#pragma unroll
+      for (int p = 0; p < S2B_PD; ++p) {
+        const int it = base + p;
+        if (it >= nstage) break;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's stage writes have landed
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (it + 1 < nstage) {
+          bexpand(pre[(p + 1) % S2B_PD], it + 1);
+          if (it + 1 + S2B_PD < nstage) bload(pre[(p + 1) % S2B_PD], it + 1 + S2B_PD);
         }
+        __builtin_amdgcn_sched_barrier(0);                   // keep the fill out of the pinned MFMA stream
+        if (active)
+#include "knn_scan2_stage.h"
       }
     }
   }
@@ -891,6 +954,47 @@ static void launch_scan2(int n_parts, int nq, hipStream_t s, const uint8_t* code
   const int nt = options().scan_nt >= 0 ? (int)(options().scan_nt != 0) : (G == 1);
   hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), lds, s, codes, n_ref, ld, lut, nq, k, range, off, parts, th,
                      wide, n_parts, G, nt);
+}
+
+// scan2_kernel over the bit-packed panel (bits[n_ref][ldb]): the same workgroup mapping and the
+// same device-decided one-limb reduction, the BITS stage fill of scan2_body.
+template <int KS, int LIMBS>
+__global__ __launch_bounds__(512) void scan2_bits_kernel(const uint8_t* __restrict__ bits, long n_ref, long ldb,
+                                                         const int8_t* __restrict__ lut, int nq, int k, long range,
+                                                         long ref_offset, uint64_t* __restrict__ parts,
+                                                         const int* __restrict__ th_init,
+                                                         const int* __restrict__ wide, int n_parts, int n_groups) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int i = blockIdx.x, G = n_groups;
+  const int slot = i / 8, group = slot % G, part = (slot / G) * 8 + i % 8;
+  if (part >= n_parts) return;                        // whole workgroup, before any barrier
+  if constexpr (LIMBS == 2 && KS <= 16) {
+    if (wide && *wide == 0) {
+      const long nqt = (nq + 15) >> 4;
+      const int8_t* lut1 = lut + nqt * 2 * KS * 1024;
+      const int* mult = reinterpret_cast<const int*>(lut1 + nqt * KS * 1024);
+      scan2_body<KS, 1, S2_QTW1, 0, true>(smem, bits, n_ref, ldb, lut1, mult, nq, k, range, ref_offset, parts,
+                                          th_init, part, group, 0);
+      return;
+    }
+  }
+  scan2_body<KS, LIMBS, 1, 0, true>(smem, bits, n_ref, ldb, lut, nullptr, nq, k, range, ref_offset, parts, th_init,
+                                    part, group, 0);
+}
+
+// two expanded stages beside the candidate lists
+template <int KS, int LB>
+static void launch_scan2_bits(int n_parts, int nq, hipStream_t s, const uint8_t* bits, long n_ref, long ldb,
+                              const int8_t* lut, int k, long range, long off, uint64_t* parts, const int* th,
+                              const int* wide) {
+  constexpr size_t lds = 2 * (size_t)s2_rows(KS) * KS * 64 + S2_CAND;
+  static_assert(lds <= S2_LDS, "LDS budget");
+  auto kern = scan2_bits_kernel<KS, LB>;
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const int G = ((nq + 15) / 16 + 7) / 8;
+  const long nwg = (long)((n_parts + 7) / 8) * 8 * G;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), lds, s, bits, n_ref, ldb, lut, nq, k, range, off, parts, th,
+                     wide, n_parts, G);
 }
 
 static int scan_parts(long n_ref, int nq) {
@@ -1058,6 +1162,43 @@ extern "C" int snvrag_knn_scan(const uint8_t* codes, int64_t n_ref, int64_t ld_c
   return 0;
 }
 
+// The scan over the bit-packed panel (include/snvrag.h): every shape runs the staged kernel.
+extern "C" int snvrag_knn_scan_bits(const uint8_t* bits, int64_t n_ref, int64_t ld_bits, int32_t n_sites_pad,
+                                    const void* lut, int32_t nq, int limbs, int k, int64_t ref_offset,
+                                    uint64_t* part_keys, int32_t n_parts, const int32_t* th_init, void* stream) {
+  SNV_CHECK_ARG(bits && lut && part_keys, "null pointer");
+  SNV_CHECK_ARG(k >= 1 && k <= 32, "k must be in [1, 32]");
+  SNV_CHECK_ARG(limbs == 1 || limbs == 2, "limbs");
+  SNV_CHECK_ARG(n_sites_pad >= 256 && n_sites_pad % 256 == 0 && n_sites_pad <= 1280 && ld_bits * 8 >= n_sites_pad,
+                "site padding: n_sites_pad a multiple of 256 up to 1280, ld_bits >= n_sites_pad / 8");
+  SNV_CHECK_ARG(ld_bits % 8 == 0 && ((uintptr_t)bits % 8) == 0, "bit rows must be 8-byte aligned");
+  SNV_CHECK_ARG(n_parts >= 1, "n_parts");
+  SNV_CHECK_ARG(n_ref + ref_offset < (1LL << 32), "panel index must fit 32 bits");
+  if (nq == 0) return 0;
+  long range = (n_ref + n_parts - 1) / n_parts;
+  range = ((range + 15) / 16) * 16;
+  if (range == 0) range = 16;
+  hipStream_t s = as_stream(stream);
+  const int8_t* L8 = (const int8_t*)lut;
+  const int* wide = (limbs == 2 && !options().knn_no_reduce)
+                        ? reinterpret_cast<const int*>(L8 + lut_tail_offset(nq, n_sites_pad) +
+                                                       (size_t)((nq + 15) / 16) * 16 * 4)
+                        : nullptr;
+  evlog_begin(s);
+#define SCAN2B(K_)                                                                                          \
+  case K_:                                                                                                  \
+    if (limbs == 2) launch_scan2_bits<K_, 2>(n_parts, nq, s, bits, n_ref, ld_bits, L8, k, range, ref_offset, part_keys, th_init, wide); \
+    else launch_scan2_bits<K_, 1>(n_parts, nq, s, bits, n_ref, ld_bits, L8, k, range, ref_offset, part_keys, th_init, nullptr);          \
+    break;
+  switch (n_sites_pad / 64) { SCAN2B(4) SCAN2B(8) SCAN2B(12) SCAN2B(16) SCAN2B(20) }
+#undef SCAN2B
+  SNV_LAUNCH_CHECK();
+  // algorithmic bytes: every panel BIT of the window once + LUT + partial lists
+  evlog_end(s, EV_KNN_SCAN, (double)n_ref * n_sites_pad / 8.0 + (double)nq * n_sites_pad * limbs +
+                            (double)n_parts * nq * k * 8.0);
+  return 0;
+}
+
 static int merge_group(int k) {
   int kp = 1;
   while (kp < k) kp <<= 1;
@@ -1111,7 +1252,7 @@ extern "C" int snvrag_knn_decode(const uint64_t* keys, int32_t nq, int k, const 
   return 0;
 }
 
-template <bool CNT>
+template <bool CNT, bool BITS = false>
 static int rag_mean_launch(int dtype_out, int64_t nq, int64_t L, int64_t D, int k, const int64_t* idx,
                            const uint8_t* codes, int64_t ld_codes, int32_t n_sites, const float* W, const float* pe,
                            const float* Ar, int tok0, int tok1, int sos, int eos, int pad, void* out, void* stream) {
@@ -1123,10 +1264,10 @@ static int rag_mean_launch(int dtype_out, int64_t nq, int64_t L, int64_t D, int 
   dim3 g((unsigned)cdiv(L, RM_P), (unsigned)cdiv(nq, RM_Q));
   hipStream_t s = as_stream(stream);
   if (dtype_out == SNVRAG_BF16)
-    hipLaunchKernelGGL((rag_mean_kernel<bf16, CNT>), g, dim3(256), 0, s, (int)nq, (int)L, (int)D, k, idx, codes,
+    hipLaunchKernelGGL((rag_mean_kernel<bf16, CNT, BITS>), g, dim3(256), 0, s, (int)nq, (int)L, (int)D, k, idx, codes,
                        (long)ld_codes, n_sites, W, pe, Ar, tok0, tok1, sos, eos, pad, (bf16*)out);
   else
-    hipLaunchKernelGGL((rag_mean_kernel<float, CNT>), g, dim3(256), 0, s, (int)nq, (int)L, (int)D, k, idx, codes,
+    hipLaunchKernelGGL((rag_mean_kernel<float, CNT, BITS>), g, dim3(256), 0, s, (int)nq, (int)L, (int)D, k, idx, codes,
                        (long)ld_codes, n_sites, W, pe, Ar, tok0, tok1, sos, eos, pad, (float*)out);
   SNV_LAUNCH_CHECK();
   return 0;
@@ -1138,6 +1279,15 @@ extern "C" int snvrag_rag_mean(int dtype_out, int64_t nq, int64_t L, int64_t D, 
                                void* out, void* stream) {
   return rag_mean_launch<false>(dtype_out, nq, L, D, k, idx, codes, ld_codes, n_sites, W, pe, Ar, tok0, tok1, sos,
                                 eos, pad, out, stream);
+}
+
+extern "C" int snvrag_rag_mean_bits(int dtype_out, int64_t nq, int64_t L, int64_t D, int k, const int64_t* idx,
+                                    const uint8_t* bits, int64_t ld_bits, int32_t n_sites, const float* W,
+                                    const float* pe, const float* Ar, int tok0, int tok1, int sos, int eos, int pad,
+                                    void* out, void* stream) {
+  SNV_CHECK_ARG(ld_bits * 8 >= n_sites, "bit row shorter than the window");
+  return rag_mean_launch<false, true>(dtype_out, nq, L, D, k, idx, bits, ld_bits, n_sites, W, pe, Ar, tok0, tok1, sos,
+                                      eos, pad, out, stream);
 }
 
 extern "C" int snvrag_rag_mean_counts(int dtype_out, int64_t nq, int64_t L, int64_t D, int k, const int64_t* idx,
@@ -1157,8 +1307,66 @@ extern "C" int snvrag_neighbor_counts(int64_t nq, int k, const int64_t* idx, con
                 "rows must be 16-byte multiples, counts row >= codes row");
   if (nq == 0) return 0;
   const long work = nq * (ld_out / 16);
-  hipLaunchKernelGGL(neighbor_counts_kernel, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, as_stream(stream),
+  hipLaunchKernelGGL(neighbor_counts_kernel<false>, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, as_stream(stream),
                      (int)nq, k, idx, codes, (long)ld, (long)row0, (long)n_rows, counts, (long)ld_out);
+  SNV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int snvrag_neighbor_counts_bits(int64_t nq, int k, const int64_t* idx, const uint8_t* bits, int64_t ld_bits,
+                                           int64_t row0, int64_t n_rows, uint8_t* counts, int64_t ld_out,
+                                           void* stream) {
+  SNV_CHECK_ARG(idx && counts && (bits || n_rows == 0), "null pointer");
+  SNV_CHECK_ARG(k >= 1 && k <= RM_KMAX, "k must be in [1, 128]");
+  SNV_CHECK_ARG(ld_bits % 2 == 0 && ld_out % 16 == 0 && ld_out >= 8 * ld_bits && ((uintptr_t)counts % 16) == 0 &&
+                    ((uintptr_t)bits % 2) == 0,
+                "bit rows must be 2-byte multiples, counts rows 16-byte multiples of at least 8 * ld_bits");
+  if (nq == 0) return 0;
+  const long work = nq * (ld_out / 16);
+  hipLaunchKernelGGL(neighbor_counts_kernel<true>, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, as_stream(stream),
+                     (int)nq, k, idx, bits, (long)ld_bits, (long)row0, (long)n_rows, counts, (long)ld_out);
+  SNV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int snvrag_panel_synth_bits(uint8_t* bits, int64_t row0, int64_t n_rows, int64_t ld_bits, int32_t n_sites,
+                                       const float* af, uint64_t seed, void* stream) {
+  SNV_CHECK_ARG(bits && af && ld_bits % 2 == 0 && ld_bits * 8 >= n_sites && row0 >= 0 && ((uintptr_t)bits % 2) == 0,
+                "bad args");
+  if (n_rows == 0) return 0;
+  const long work = n_rows * (ld_bits / 2);
+  const int grid = (int)std::min<long>(cdiv(work, 256), 65536);
+  hipLaunchKernelGGL(panel_synth_bits_kernel, dim3(grid), dim3(256), 0, as_stream(stream), bits, (long)n_rows,
+                     (long)ld_bits, n_sites, af, seed, (long)row0);
+  SNV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int snvrag_panel_pack_bits(const uint8_t* codes, int64_t n, int64_t ld, uint8_t* bits, int64_t ld_bits,
+                                      void* stream) {
+  SNV_CHECK_ARG((codes && bits) || n == 0, "null pointer");
+  SNV_CHECK_ARG(n >= 0 && ld % 16 == 0 && ld_bits % 2 == 0 && ld_bits * 8 >= ld && ((uintptr_t)codes % 16) == 0 &&
+                    ((uintptr_t)bits % 2) == 0,
+                "codes rows must be 16-byte multiples, bit rows 2-byte multiples of at least ld / 8");
+  if (n == 0) return 0;
+  const long work = n * (ld_bits / 2);
+  SNV_CHECK_ARG(cdiv(work, 256) > 0 && work / 256 < (1L << 31) - 1, "panel too large for one launch");
+  hipLaunchKernelGGL(panel_pack_bits_kernel, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, as_stream(stream), codes,
+                     (long)n, (long)ld, bits, (long)ld_bits);
+  SNV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int snvrag_panel_unpack_rows(const uint8_t* bits, int64_t n_ref, int64_t ld_bits, const int64_t* rows,
+                                        int64_t n_rows, uint8_t* out, int64_t ld_out, void* stream) {
+  SNV_CHECK_ARG(n_rows == 0 || (rows && out && (bits || n_ref == 0)), "null pointer");
+  SNV_CHECK_ARG(n_ref >= 0 && n_rows >= 0 && ld_bits % 2 == 0 && ld_out % 16 == 0 && ((uintptr_t)out % 16) == 0 &&
+                    ((uintptr_t)bits % 2) == 0,
+                "bit rows must be 2-byte multiples, output rows 16-byte multiples");
+  if (n_rows == 0) return 0;
+  const long work = n_rows * (ld_out / 16);
+  hipLaunchKernelGGL(panel_unpack_rows_kernel, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, as_stream(stream), bits,
+                     (long)n_ref, (long)ld_bits, rows, (long)n_rows, out, (long)ld_out);
   SNV_LAUNCH_CHECK();
   return 0;
 }

@@ -57,10 +57,11 @@ class EmbeddingRAGDataset(TrainDataset):
                  ref_gt: Optional[np.ndarray] = None, ref_pos: Optional[np.ndarray] = None,
                  embedding_layer=None, build_ref_data: bool = True, n_gpu: int = 1,
                  maf_mask_percentage: int = 10, use_dynamic_mask: bool = False, name: str = "default",
-                 index_cache_bytes: int = 64 << 30, panel_cache: str = "window"):
+                 index_cache_bytes: int = 64 << 30, panel_cache: str = "window", panel_codes: str = "u8"):
         super().__init__(vocab, vcf, pos, panel, freq, window, type_to_idx, pop_to_idx, pos_to_idx)
         if panel_cache not in ("window", "fresh"):
             raise ValueError("panel_cache must be 'window' (the reference's per-window snapshot) or 'fresh'")
+        self.panel_codes = check_panel_codes(panel_codes)
         self.panel_cache = panel_cache
         self._panel_snap = None          # (window, W snapshot, A_r snapshot, weights token) of the cached window
         self.maf_mask_percentage, self.use_dynamic_mask = maf_mask_percentage, use_dynamic_mask
@@ -181,11 +182,17 @@ class EmbeddingRAGDataset(TrainDataset):
             self.window_masks = [sequence_padding(m, "int") for m in self.raw_window_masks]
             self.mask_version += 1
 
+    def set_panel_codes(self, panel_codes: str) -> None:
+        """Layout of the windows' panel indexes built from now on: "u8" or "bits" (bit-packed)."""
+        self.panel_codes = check_panel_codes(panel_codes)
+        self._index_cache.clear()
+
     def panel_index(self, w: int, device) -> "object":
         from ..retrieval import PanelIndex
         idx = self._index_cache.get(w)
-        if idx is None or idx.codes.device != torch.device(device):
-            idx = panel_index_of(self.ref_alleles[w], self.ref_af_windows[w], device, self.panel_shard)
+        if idx is None or idx.device != torch.device(device):
+            idx = panel_index_of(self.ref_alleles[w], self.ref_af_windows[w], device, self.panel_shard,
+                                 self.panel_codes)
             self._index_cache[w] = idx
             while sum(i.nbytes for i in self._index_cache.values()) > self._index_cache_bytes and \
                     len(self._index_cache) > 1:
@@ -201,10 +208,11 @@ class EmbeddingRAGDataset(TrainDataset):
 
     @classmethod
     def from_arrays(cls, vocab, vcf, pos, pop_list, freq, window_bounds, pop_to_idx, pos_to_idx,
-                    ref_gt, ref_pos, embedding_layer=None, name="default", type_to_idx=None) -> "EmbeddingRAGDataset":
+                    ref_gt, ref_pos, embedding_layer=None, name="default", type_to_idx=None,
+                    **kw) -> "EmbeddingRAGDataset":
         win = Window(np.asarray(window_bounds)[:, 0], np.asarray(window_bounds)[:, 1])
         return cls(vocab, vcf, pos, PanelData(pop_list), freq, win, type_to_idx or {}, pop_to_idx, pos_to_idx,
-                   ref_gt=ref_gt, ref_pos=ref_pos, embedding_layer=embedding_layer, name=name)
+                   ref_gt=ref_gt, ref_pos=ref_pos, embedding_layer=embedding_layer, name=name, **kw)
 
 
 def _weights_token(P) -> tuple:
@@ -228,13 +236,23 @@ def h2d(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
     return t.to(dev, non_blocking=True)
 
 
-def panel_index_of(alleles: np.ndarray, ref_af: np.ndarray, device, shard=None):
-    """PanelIndex of one window's panel, or of this rank's contiguous range of it."""
+def check_panel_codes(panel_codes: str) -> str:
+    if panel_codes not in ("u8", "bits"):
+        raise ValueError("panel_codes must be 'u8' (one byte per site, the default) or 'bits' (bit-packed, "
+                         f"an eighth of the HBM); got {panel_codes!r}")
+    return panel_codes
+
+
+def panel_index_of(alleles: np.ndarray, ref_af: np.ndarray, device, shard=None, panel_codes: str = "u8"):
+    """PanelIndex of one window's panel, or of this rank's contiguous range of it; ``panel_codes``
+    "bits" builds the bit-packed layout (packed on the host, uploaded as bits)."""
     from ..retrieval import PanelIndex
+    packed = check_panel_codes(panel_codes) == "bits"
     if shard is None:
-        return PanelIndex.from_alleles(alleles, ref_af, device)
+        return PanelIndex.from_alleles(alleles, ref_af, device, packed=packed)
     r0, r1 = shard.bounds(alleles.shape[0])
-    return PanelIndex.from_alleles(alleles[r0:r1], ref_af, device, ref_offset=r0, n_total=alleles.shape[0])
+    return PanelIndex.from_alleles(alleles[r0:r1], ref_af, device, ref_offset=r0, n_total=alleles.shape[0],
+                                   packed=packed)
 
 
 def retrieve(ds, batch: dict, embedding_layer, device, k: int, masks: List[np.ndarray],
@@ -356,9 +374,9 @@ def retrieve(ds, batch: dict, embedding_layer, device, k: int, masks: List[np.nd
                                              *(uniq if uniq is not None else (None, None))))
         else:
             if nb == B and rows == list(range(B)):      # one window, batch order: no scatter
-                K.rag_mean(idx, index.codes, n, P.W, P.pe, Ar_emb, L, eng.dtype, out=rag_mean, counts=counts)
+                index.rag_mean(idx, P.W, P.pe, Ar_emb, L, eng.dtype, out=rag_mean, counts=counts)
             else:
-                means = K.rag_mean(idx, index.codes, n, P.W, P.pe, Ar_emb, L, eng.dtype, counts=counts)
+                means = index.rag_mean(idx, P.W, P.pe, Ar_emb, L, eng.dtype, counts=counts)
                 rag_mean[rows_t] = means[:nb]
                 rag_mean[rows_t + B] = means[nb:]
         if dense and not train:
@@ -369,7 +387,7 @@ def retrieve(ds, batch: dict, embedding_layer, device, k: int, masks: List[np.nd
                                           "a sharded panel returns their counts only")
             if dense_out is None:
                 dense_out = torch.zeros(2 * B, k, L, D, device=dev, dtype=torch.float32)
-            e = K.rag_mean(idx.reshape(-1, 1), index.codes, n, P.W, P.pe, Ar_emb, L, torch.float32)
+            e = index.rag_mean(idx.reshape(-1, 1), P.W, P.pe, Ar_emb, L, torch.float32)
             e = e.view(2 * nb, k, L, D)
             dense_out[rows_t] = e[:nb]
             dense_out[rows_t + B] = e[nb:]

@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from .dataset import INFER_WINDOW_LEN, InferDataset, PanelData
-from .embedding_rag_dataset import panel_index_of, retrieve
+from .embedding_rag_dataset import check_panel_codes, panel_index_of, retrieve
 from .utils import MAX_SEQ_LEN, sequence_padding
 
 REFERENCE_INDEX_WINDOW = 510     # embedding_rag_infer_dataset.py:16
@@ -47,8 +47,9 @@ class EmbeddingRAGInferDataset(InferDataset):
                  ref_vcf_path=None, embedding_layer=None, build_ref_data: bool = True, n_gpu: int = 1,
                  build_index: bool = True, name: str = "infer", ref_gt: Optional[np.ndarray] = None,
                  ref_pos: Optional[np.ndarray] = None, index_window_len: int = REFERENCE_INDEX_WINDOW,
-                 window_len: int = INFER_WINDOW_LEN, index_cache_bytes: int = 64 << 30):
+                 window_len: int = INFER_WINDOW_LEN, index_cache_bytes: int = 64 << 30, panel_codes: str = "u8"):
         super().__init__(vocab, vcf, pos, panel, freq, type_to_idx, pop_to_idx, pos_to_idx, window_len=window_len)
+        self.panel_codes = check_panel_codes(panel_codes)
         self.embedding_layer = embedding_layer
         self.embed_dim = embedding_layer.embed_size if embedding_layer is not None else 384
         self.index_window_len = int(index_window_len)
@@ -120,10 +121,16 @@ class EmbeddingRAGInferDataset(InferDataset):
         self.panel_shard = shard
         self._index_cache.clear()
 
+    def set_panel_codes(self, panel_codes: str) -> None:
+        """Layout of the windows' panel indexes built from now on: "u8" or "bits" (bit-packed)."""
+        self.panel_codes = check_panel_codes(panel_codes)
+        self._index_cache.clear()
+
     def panel_index(self, w: int, device) -> "object":
         idx = self._index_cache.get(w)
-        if idx is None or idx.codes.device != torch.device(device):
-            idx = panel_index_of(self.ref_alleles[w], self.ref_af_windows[w], device, self.panel_shard)
+        if idx is None or idx.device != torch.device(device):
+            idx = panel_index_of(self.ref_alleles[w], self.ref_af_windows[w], device, self.panel_shard,
+                                 self.panel_codes)
             self._index_cache[w] = idx
             while sum(i.nbytes for i in self._index_cache.values()) > self._index_cache_bytes and \
                     len(self._index_cache) > 1:

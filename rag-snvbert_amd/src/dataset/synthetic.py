@@ -154,7 +154,7 @@ POPS = ["AFR", "AMR", "EAS", "EUR", "SAS"]
 
 
 def make_rag_dataset(n_samples: int = 8, n_sites: int = 512, n_windows: int = 2, n_ref_samples: int = 64,
-                     seed: int = 0, name: str = "val"):
+                     seed: int = 0, name: str = "val", **kw):
     """In-memory EmbeddingRAGDataset over synthetic data with the reference's file
     contract (GT [sites, samples, 2], Freq.npy [4, n_pop+1, sites], window bounds,
     pop_to_idx / pos_to_idx).  Returns (dataset, vocab)."""
@@ -178,7 +178,7 @@ def make_rag_dataset(n_samples: int = 8, n_sites: int = 512, n_windows: int = 2,
     bounds = np.array([[w * n_sites, (w + 1) * n_sites] for w in range(n_windows)])
     ds = EmbeddingRAGDataset.from_arrays(vocab, vcf.astype(np.int8), pos, pops, freq, bounds,
                                          {p: i for i, p in enumerate(POPS)},
-                                         {int(p): i for i, p in enumerate(pos)}, ref, pos, name=name)
+                                         {int(p): i for i, p in enumerate(pos)}, ref, pos, name=name, **kw)
     return ds, vocab
 
 
@@ -216,7 +216,7 @@ def make_infer_arrays(n_sites: int = 1300, n_samples: int = 3, n_ref_samples: in
                 ref_pos=ori_pos[ref_rows], source=src)
 
 
-def make_infer_dataset(a: dict = None, index_window_len: int = 510, **kw):
+def make_infer_dataset(a: dict = None, index_window_len: int = 510, panel_codes: str = "u8", **kw):
     """EmbeddingRAGInferDataset over ``make_infer_arrays`` data (or ``a``).  Returns (dataset, vocab)."""
     from .embedding_rag_infer_dataset import EmbeddingRAGInferDataset
     from .vocab import WordVocab
@@ -224,5 +224,5 @@ def make_infer_dataset(a: dict = None, index_window_len: int = 510, **kw):
     vocab = WordVocab(POPS)
     ds = EmbeddingRAGInferDataset.from_arrays(vocab, a["vcf"], a["pos"], a["pops"], a["freq"], a["pop_to_idx"],
                                               a["pos_to_idx"], a["ref_gt"], a["ref_pos"],
-                                              index_window_len=index_window_len)
+                                              index_window_len=index_window_len, panel_codes=panel_codes)
     return ds, vocab

@@ -59,6 +59,9 @@ def parse_args(argv=None):
     p.add_argument("--mask_rate", type=float, default=0.3,
                    help="synthetic: fraction of panel sites absent from the target (C5 sweep 0.1..0.9)")
     p.add_argument("--no_vcf", action="store_true")
+    p.add_argument("--panel_codes", default="u8", choices=["u8", "bits"],
+                   help="layout of the HBM panel index: one byte per site, or bit-packed (1/8 of the memory, "
+                        "identical neighbours)")
     p.add_argument("--seed", type=int, default=0, help="weight init without --check_point (synthetic runs)")
     p.add_argument("--dist_backend", default="nccl", choices=["nccl", "gloo"],
                    help="WORLD_SIZE > 1 (torch.distributed.run, one process per GPU): nccl (= RCCL) or gloo "
@@ -131,11 +134,12 @@ def build_dataset(args):
                                                 args.type_path, args.pop_path, args.pos_path,
                                                 ref_vcf_path=args.ref_panel, window_len=args.window_len,
                                                 index_window_len=args.index_window_len)
+        ds.set_panel_codes(args.panel_codes)
         return ds, vocab
     from .dataset.synthetic import make_infer_arrays, make_infer_dataset
     a = make_infer_arrays(args.synthetic_sites, args.synthetic, args.synthetic_ref, missing_rate=args.mask_rate,
                           seed=11)
-    return make_infer_dataset(a, index_window_len=args.index_window_len)
+    return make_infer_dataset(a, index_window_len=args.index_window_len, panel_codes=args.panel_codes)
 
 
 def rank_rows(n_rows: int, rank: int, world: int):

@@ -319,6 +319,23 @@ def knn_scan(codes: torch.Tensor, n_sites_pad: int, lut: torch.Tensor, nq: int, 
     return parts
 
 
+def knn_scan_bits(bits: torch.Tensor, n_sites_pad: int, lut: torch.Tensor, nq: int, limbs: int, k: int,
+                  ref_offset: int = 0, n_parts: Optional[int] = None,
+                  th_init: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``knn_scan`` over the bit-packed panel (u8 [n_ref, ld_bits], ``panel_pack_bits``): the same
+    part keys bit for bit."""
+    assert bits.dtype == torch.uint8 and bits.dim() == 2
+    n_ref, ldb = bits.shape
+    if n_parts is None:
+        n_parts = N.lib().snvrag_knn_scan_parts(n_ref, nq)
+    parts = torch.empty(n_parts, nq, k, device=bits.device, dtype=torch.int64)
+    if th_init is not None:
+        assert th_init.dtype == torch.int32 and th_init.numel() == nq
+    check(N.lib().snvrag_knn_scan_bits(ptr(_c(bits)), n_ref, ldb, n_sites_pad, ptr(lut), nq, limbs, k, ref_offset,
+                                       ptr(parts), n_parts, ptr(th_init), stream_ptr()), "knn_scan_bits")
+    return parts
+
+
 def knn_threshold(keys: torch.Tensor, k: int) -> torch.Tensor:
     """Per-query strict start threshold (int32 [nq]) from merged keys [nq, k]."""
     nq = keys.shape[0]
@@ -406,11 +423,12 @@ def knn_emb_search(Et: torch.Tensor, Q: torch.Tensor, k: int, rn: torch.Tensor, 
 
 def rag_mean(idx: torch.Tensor, codes: torch.Tensor, n_sites: int, W: torch.Tensor, pe: torch.Tensor,
              Ar: Optional[torch.Tensor], L: int, dtype: torch.dtype, tok0=5, tok1=6, sos=2, eos=3, pad=0,
-             out: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None):
+             out: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None, bits: bool = False):
     """[nq, L, D] mean over the k neighbours of their complete-token embeddings; ``out`` (e.g. the
     rag half of the encoder's input block) is written in place.  ``counts`` (u8 [nq, ld], the
     per-site alt-allele counts over the neighbours, see ``neighbor_counts``) replaces the panel
-    rows ``codes[idx]`` (sharded panels; ``codes`` is then unused)."""
+    rows ``codes[idx]`` (sharded panels; ``codes`` is then unused).  ``bits``: ``codes`` is the
+    bit-packed panel (``panel_pack_bits``), read in place."""
     nq, k = idx.shape
     D = W.shape[1]
     if out is None:
@@ -422,6 +440,11 @@ def rag_mean(idx: torch.Tensor, codes: torch.Tensor, n_sites: int, W: torch.Tens
                                              n_sites, ptr(_c(W)), ptr(_c(pe)), ptr(Ar), tok0, tok1, sos, eos, pad,
                                              ptr(out), stream_ptr()), "rag_mean_counts")
         return out
+    if bits:
+        check(N.lib().snvrag_rag_mean_bits(_dt(dtype), nq, L, D, k, ptr(_c(idx)), ptr(_c(codes)), codes.shape[1],
+                                           n_sites, ptr(_c(W)), ptr(_c(pe)), ptr(Ar), tok0, tok1, sos, eos, pad,
+                                           ptr(out), stream_ptr()), "rag_mean_bits")
+        return out
     check(N.lib().snvrag_rag_mean(_dt(dtype), nq, L, D, k, ptr(_c(idx)), ptr(_c(codes)), codes.shape[1], n_sites,
                                   ptr(_c(W)), ptr(_c(pe)), ptr(Ar), tok0, tok1, sos, eos, pad, ptr(out),
                                   stream_ptr()), "rag_mean")
@@ -429,14 +452,19 @@ def rag_mean(idx: torch.Tensor, codes: torch.Tensor, n_sites: int, W: torch.Tens
 
 
 def neighbor_counts(idx: torch.Tensor, codes: torch.Tensor, row0: int, ld_out: Optional[int] = None,
-                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, bits: bool = False) -> torch.Tensor:
     """u8 [nq, ld_out]: per-site alt-allele counts over the neighbours ``idx`` (global, int64
-    [nq, k]) that fall in this shard's rows [row0, row0 + codes.shape[0])."""
+    [nq, k]) that fall in this shard's rows [row0, row0 + codes.shape[0]).  ``bits``: ``codes`` is
+    the bit-packed shard (``panel_pack_bits``); ld_out defaults to its 8 * ld_bits sites."""
     nq, k = idx.shape
     n_rows, ld = codes.shape
-    ld_out = ld_out or ld
+    ld_out = ld_out or (8 * ld if bits else ld)
     if out is None:
         out = torch.empty(nq, ld_out, device=idx.device, dtype=torch.uint8)
+    if bits:
+        check(N.lib().snvrag_neighbor_counts_bits(nq, k, ptr(_c(idx)), ptr(_c(codes)), ld, row0, n_rows, ptr(out),
+                                                  ld_out, stream_ptr()), "neighbor_counts_bits")
+        return out
     check(N.lib().snvrag_neighbor_counts(nq, k, ptr(_c(idx)), ptr(_c(codes)), ld, row0, n_rows, ptr(out), ld_out,
                                          stream_ptr()), "neighbor_counts")
     return out
@@ -464,6 +492,42 @@ def panel_synth(n_ref: int, n_sites: int, af: torch.Tensor, seed: int, ld: Optio
     check(N.lib().snvrag_panel_synth_rows(ptr(codes), row0, n_ref, ld, n_sites, ptr(_c(af)), seed, stream_ptr()),
           "panel_synth")
     return codes
+
+
+def panel_synth_bits(n_ref: int, n_sites: int, af: torch.Tensor, seed: int, ld_bits: Optional[int] = None,
+                     row0: int = 0) -> torch.Tensor:
+    """``panel_synth``'s rows written straight as bits (u8 [n_ref, ld_bits], site s = bit s & 7 of
+    byte s >> 3): the u8 form of the panel never exists."""
+    N.require_gpu(af)
+    ld_bits = ld_bits or max(256, ((n_sites + 255) // 256) * 256) // 8
+    bits = torch.empty(n_ref, ld_bits, device=af.device, dtype=torch.uint8)
+    check(N.lib().snvrag_panel_synth_bits(ptr(bits), row0, n_ref, ld_bits, n_sites, ptr(_c(af)), seed, stream_ptr()),
+          "panel_synth_bits")
+    return bits
+
+
+def panel_pack_bits(codes: torch.Tensor) -> torch.Tensor:
+    """u8 0/1 codes [n, ld] on the device -> bits u8 [n, ld / 8] (numpy.packbits(bitorder="little")
+    of each row)."""
+    N.require_gpu(codes)
+    assert codes.dtype == torch.uint8 and codes.dim() == 2 and codes.shape[1] % 16 == 0
+    n, ld = codes.shape
+    bits = torch.empty(n, ld // 8, device=codes.device, dtype=torch.uint8)
+    check(N.lib().snvrag_panel_pack_bits(ptr(_c(codes)), n, ld, ptr(bits), ld // 8, stream_ptr()), "panel_pack_bits")
+    return bits
+
+
+def panel_unpack_rows(bits: torch.Tensor, rows: torch.Tensor, ld_out: Optional[int] = None) -> torch.Tensor:
+    """u8 [len(rows), ld_out] 0/1 codes of the bit rows ``rows`` (int64, local row numbers); rows
+    outside [0, n_ref) come out zero.  ld_out defaults to the 8 * ld_bits sites of a bit row."""
+    N.require_gpu(bits, rows)
+    assert bits.dtype == torch.uint8 and bits.dim() == 2 and rows.dtype == torch.int64 and rows.dim() == 1
+    n_ref, ldb = bits.shape
+    ld_out = ld_out or 8 * ldb
+    out = torch.empty(rows.numel(), ld_out, device=bits.device, dtype=torch.uint8)
+    check(N.lib().snvrag_panel_unpack_rows(ptr(_c(bits)), n_ref, ldb, ptr(_c(rows)), rows.numel(), ptr(out), ld_out,
+                                           stream_ptr()), "panel_unpack_rows")
+    return out
 
 
 def encoder_forward(x: torch.Tensor, layers: Sequence["N.LayerW"], heads: int, ws: torch.Tensor) -> torch.Tensor:

@@ -196,10 +196,12 @@ def kernel_ops(index, W: torch.Tensor, site_mask: torch.Tensor, k: int, limbs: i
 
     def codes(uniq):
         i = uniq - index.ref_offset
+        if index.packed:       # the gather kernel zeroes the rows this shard does not own
+            return index.rows(i)
         own = (i >= 0) & (i < index.codes.shape[0])
         out = torch.zeros(uniq.numel(), index.codes.shape[1], device=uniq.device, dtype=torch.uint8)
         out[own] = index.codes[i[own]]
         return out
 
     return ShardOps(keys=keys, merge=K.topk_merge, decode=K.knn_decode,
-                    counts=lambda idx: K.neighbor_counts(idx, index.codes, index.ref_offset), codes=codes)
+                    counts=index.neighbor_counts, codes=codes)

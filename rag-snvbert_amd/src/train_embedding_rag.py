@@ -60,6 +60,9 @@ def parse_args(argv=None):
     p.add_argument("--panel", default="sharded", choices=["sharded", "replicated"],
                    help="DDP: each rank holds 1/world of every window's panel and serves every rank's "
                         "queries (SURVEY §8e), or every rank holds the whole panel")
+    p.add_argument("--panel_codes", default="u8", choices=["u8", "bits"],
+                   help="layout of the HBM panel index: one byte per site, or bit-packed (1/8 of the memory, "
+                        "identical neighbours)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--dropout", type=float, default=0.1,
                    help="model dropout (the reference's BERT default 0.1); another value sets every dropout layer")
@@ -90,6 +93,8 @@ def build_data(args, rank: int, world: int):
                                         args.synthetic_ref, seed=args.seed, name="train")
         val, _ = make_rag_dataset(max(2, args.synthetic // 4), args.synthetic_sites, args.synthetic_windows,
                                   args.synthetic_ref, seed=args.seed + 1, name="val")
+        for ds in (train, val):
+            ds.set_panel_codes(args.panel_codes)
     else:
         raise SystemExit("reading the reference's H5/VCF inputs needs h5py and scikit-allel, which this image "
                          "does not have; run with --synthetic N (in-memory data with the same file contract)")

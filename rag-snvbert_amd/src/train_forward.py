@@ -250,8 +250,14 @@ def neighbour_embeddings(emb, groups: List[NeighbourGroup], B: int, L: int, dens
         if p > 0 or dense or g.uniq is not None:
             m = _unique_neighbour_embed(emb.tokenizer.weight, Ar, idx, g, pe, L, p, dense)
         else:
-            m = rag_mean_train(emb.tokenizer.weight, Ar, idx, g.index.codes, g.index.n_sites, pe, L,
-                               counts=g.counts).float()
+            counts, codes = g.counts, None
+            if getattr(g.index, "packed", False):
+                # bit-packed panel: the neighbours' per-site counts straight from their bit rows —
+                # the integers the u8 rows would sum to, so the same mean and the same backward
+                counts = counts if counts is not None else g.index.neighbor_counts(idx)
+            elif counts is None:
+                codes = g.index.codes
+            m = rag_mean_train(emb.tokenizer.weight, Ar, idx, codes, g.index.n_sites, pe, L, counts=counts).float()
         nb = g.rows.numel()
         rows_out += [g.rows, g.rows + B]
         vals += [m[:nb], m[nb:]]
@@ -294,10 +300,10 @@ def _unique_neighbour_embed(W: torch.Tensor, Ar: torch.Tensor, idx: torch.Tensor
         # same sorted ranks, the unique list padded to nq * k with its last value (the fused
         # kernels touch only the rows ``inv`` names)
         uniq, inv = _unique_padded(idx.clamp(min=0))
-        rows_codes = g.index.codes[uniq - g.index.ref_offset]
+        rows_codes = g.index.rows(uniq - g.index.ref_offset)
     else:
         uniq, inv = torch.unique(idx.clamp(min=0), return_inverse=True)
-        rows_codes = g.index.codes[uniq - g.index.ref_offset]
+        rows_codes = g.index.rows(uniq - g.index.ref_offset)
     U = uniq.numel()
     if fused:
         # fused: no [U, L, D] embeddings, one dropout mask per unique neighbour (csrc/train.hip)
@@ -327,7 +333,7 @@ def neighbour_mean_dropout(W: torch.Tensor, Ar: torch.Tensor, idx: torch.Tensor,
     dropout semantics (each unique neighbour re-encoded once, embedding_rag_dataset.py:404-417,
     then bert.py:171-183's mean over k), differentiable in W and Ar."""
     from types import SimpleNamespace
-    index = SimpleNamespace(codes=codes, n_sites=n_sites, ref_offset=0)
+    index = SimpleNamespace(codes=codes, rows=lambda i: codes[i], n_sites=n_sites, ref_offset=0)
     g = NeighbourGroup(rows=idx.new_zeros(0), idx_h1=idx, idx_h2=idx[:0], index=index)
     return _unique_neighbour_embed(W, Ar, idx, g, pe, L, p, False).to(train_dtype())
 
