@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SNVRAG_ABI_VERSION 30
+#define SNVRAG_ABI_VERSION 31
 
 enum { SNVRAG_F32 = 0, SNVRAG_BF16 = 1 };
 enum { SNVRAG_ACT_NONE = 0, SNVRAG_ACT_GELU = 1, SNVRAG_ACT_LRELU = 2, SNVRAG_ACT_SIGMOID = 3 };
@@ -649,6 +649,74 @@ int snvrag_linear_dw_parts_det(int64_t M, int64_t N, int64_t K, const void* dy, 
  * softmax) and gt [M, 4] = (p00, p01, p10, p11).  gt 16-byte aligned. */
 int snvrag_infer_post(int64_t M, const float* probs_h1, const float* probs_h2, float* p1, float* p2,
                       float* gt, void* stream);
+
+/* Inference post-processing written straight into the site-major result arrays (replaces
+ * infer_embedding_rag.py:145-152 AND the geometry step :171-203 — slice tokens [1, 1 + window_len),
+ * [W, S, L] -> [W * window_len, S], fit to n_variants): the arithmetic of snvrag_infer_post (one
+ * shared device function: the same bits) for batch row b = (sample rows[b], window rows[B + b]);
+ * token t in [1, window_len] goes to site row w * window_len + t - 1, column sample, dropped when the
+ * row is >= n_variants.  hap1, hap2 f32 [n_variants][S]; gp f32 [n_variants][S][4] (16-byte aligned);
+ * mask_out i64 [n_variants][S] = mask [B][L] at the same places.  The caller zeroes the arrays once:
+ * rows no window covers stay zero, as the host geometry pads them.  rows_dev is the per-batch row
+ * table of snvrag_batch_features on the device, rows_host the same table on the host (checked here:
+ * a sample outside [0, S) or a negative window is refused, never a stray store).
+ * window_len in [1, L - 1]; B * L < 2^31.  One process only: ranks of a multi-process run hold
+ * disjoint rows and keep the per-row gather. */
+int snvrag_infer_scatter(int64_t B, int32_t L, const float* probs_h1, const float* probs_h2,
+                         const int64_t* mask, const int32_t* rows_dev, const int32_t* rows_host,
+                         int32_t window_len, int64_t n_variants, int64_t S, float* hap1, float* hap2,
+                         float* gp, int64_t* mask_out, void* stream);
+
+/* Device-resident featurisation (opt-in; replaces the per-item host work of dataset.py
+ * TrainDataset.__getitem__ :455-582 / InferDataset.__getitem__ :818-900, the v18 overrides
+ * embedding_rag_dataset.py:486-555 and embedding_rag_infer_dataset.py:226-248, vocab.py:153-170
+ * to_seq and utils.py:121-132 sequence_padding, plus the collate and the host -> device copy of the
+ * batch).  The static inputs are uploaded once per dataset:
+ *   gt_bits        u8 [2 S][ld_bits]: row 2 s + h = haplotype h of sample s over the rows of the
+ *                  dataset's vcf array, in the bit layout above (site r = bit r & 7 of byte r >> 3);
+ *   win_off        i32 [W + 1]: window w owns entries [win_off[w], win_off[w + 1]) of the three site
+ *                  tables; max_window_sites = the largest such count (n below);
+ *   site_row       i32: row in vcf, or -1 for a site absent from the target (allele 0);
+ *   freq_col       i32: column of the frequency table;
+ *   pos_norm       f32: the window's min-max normalised position, computed on the host exactly as
+ *                  position_normalize -> sequence_padding -> float32 do (NaN of a one-site window
+ *                  included): the kernel does no float arithmetic;
+ *   win_mask       u8 [W][L]: the padded 0/1 mask every item of the window carries;
+ *   freq           f32 [4][n_pop][n_cols] (REF, HET, HOM, AF), global_row = the GLOBAL population row;
+ *   pop_of_sample  i32 [S], each in [0, n_pop).
+ * Entries of site_row / freq_col must be < 8 ld_bits / < n_cols (the table builder's contract).
+ * Per batch: rows i32 [3][B] = sample[b], window[b], flags[b] (bit 0: metric mask all zero — the
+ * DistributedWindowSampler padding duplicate: same tokens, zero mask), on the device (rows_dev) and
+ * on the host (rows_host, checked here).
+ * Outputs, caller-allocated and contiguous: tokens i64 [2 B][L] (hap_1 rows, then hap_2 rows),
+ * mask_out i64 [B][L], floats f32 [6][B][L] (pos, af, af_p, ref, het, hom), labels i64 [3][B][L]
+ * (hap_1_label, hap_2_label, gt_label = (h1 << 1) + h2) or NULL.  i64 outputs 16-byte, floats 8-byte
+ * aligned.  With n the window's site count: the base token is sos at t = 0, tok0 / tok1 by allele
+ * at 1 <= t <= n, eos at t = n + 1 when n + 1 < L, pad elsewhere; then the mask id wherever
+ * win_mask[w][t] is set.  Floats and labels hold the site's value at 1 <= t <= n and 0 elsewhere;
+ * af reads population row global_row, af_p / ref / het / hom the sample's population.
+ * Refused: L outside [2, 1030], n + 1 > L, a sample or window index out of range, B * L >= 2^31. */
+typedef struct {
+  const uint8_t* gt_bits;
+  const int32_t* win_off;
+  const int32_t* site_row;
+  const int32_t* freq_col;
+  const float* pos_norm;
+  const uint8_t* win_mask;
+  const float* freq;
+  const int32_t* pop_of_sample;
+  int64_t ld_bits;
+  int64_t n_cols;
+  int32_t n_samples;
+  int32_t n_windows;
+  int32_t max_window_sites;
+  int32_t n_pop;
+  int32_t global_row;
+} snvrag_feature_tables_t;
+int snvrag_batch_features(const snvrag_feature_tables_t* tables, const int32_t* rows_dev,
+                          const int32_t* rows_host, int64_t B, int32_t L, int sos, int eos, int pad, int mask,
+                          int tok0, int tok1, int64_t* tokens, int64_t* mask_out, float* floats, int64_t* labels,
+                          void* stream);
 
 /* self tests of MFMA operand/accumulator layouts used by the kernels (GPU only):
  * returns 0 when the i8 / bf16 / f32 MFMA maps match the CPU product. */

@@ -430,24 +430,81 @@ extern "C" int snvrag_gt_head(int64_t M, const float* p1, const float* p2, const
 // --------------------------------------------------------- infer post-process --
 // infer_embedding_rag.py:145-152: the heads' probabilities go through softmax AGAIN,
 // p = softmax(probs)[..., 1]; gt = [(1-p1)(1-p2), (1-p1)p2, p1(1-p2), p1 p2].
-__global__ __launch_bounds__(256) void infer_post_kernel(long M, const float* __restrict__ ph1,
-                                                         const float* __restrict__ ph2, float* __restrict__ p1o,
-                                                         float* __restrict__ p2o, float* __restrict__ gt) {
-  const long m = (long)blockIdx.x * 256 + threadIdx.x;
-  if (m >= M) return;
-  auto p_alt = [](float a, float b) {          // softmax([a, b])[1]
-    const float mx = fmaxf(a, b), ea = expf(a - mx), eb = expf(b - mx);
-    return eb / (ea + eb);
-  };
-  const float p1 = p_alt(ph1[2 * m], ph1[2 * m + 1]), p2 = p_alt(ph2[2 * m], ph2[2 * m + 1]);
-  p1o[m] = p1;
-  p2o[m] = p2;
+// The arithmetic of both kernels below (infer_post_kernel and infer_scatter_kernel): one
+// definition, so the scattered results are the bits of the row-major ones.
+__device__ __forceinline__ float post_p_alt(float a, float b) {          // softmax([a, b])[1]
+  const float mx = fmaxf(a, b), ea = expf(a - mx), eb = expf(b - mx);
+  return eb / (ea + eb);
+}
+__device__ __forceinline__ f32x4 post_gt(float p1, float p2) {
   f32x4 g;
   g[0] = (1.f - p1) * (1.f - p2);
   g[1] = (1.f - p1) * p2;
   g[2] = p1 * (1.f - p2);
   g[3] = p1 * p2;
-  reinterpret_cast<f32x4*>(gt)[m] = g;
+  return g;
+}
+
+__global__ __launch_bounds__(256) void infer_post_kernel(long M, const float* __restrict__ ph1,
+                                                         const float* __restrict__ ph2, float* __restrict__ p1o,
+                                                         float* __restrict__ p2o, float* __restrict__ gt) {
+  const long m = (long)blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  const float p1 = post_p_alt(ph1[2 * m], ph1[2 * m + 1]), p2 = post_p_alt(ph2[2 * m], ph2[2 * m + 1]);
+  p1o[m] = p1;
+  p2o[m] = p2;
+  reinterpret_cast<f32x4*>(gt)[m] = post_gt(p1, p2);
+}
+
+// infer_post + the geometry step of infer_embedding_rag.py:171-203 in one pass: batch row b
+// (sample rows[b], window rows[B + b]) token t in [1, window_len] lands in site row
+// w * window_len + t - 1, column sample, of the site-major result arrays.  A workgroup takes a
+// tile of 64 tokens x 16 batch rows: the probabilities are read token-fastest (contiguous in a
+// batch row), turned through the LDS and written batch-row-fastest, so the rows of a window-major
+// batch (consecutive samples) store contiguous runs of every site row.
+constexpr int SC_T = 64, SC_B = 16;
+__global__ __launch_bounds__(256) void infer_scatter_kernel(int B, int L, const float* __restrict__ ph1,
+                                                            const float* __restrict__ ph2,
+                                                            const int64_t* __restrict__ mask,
+                                                            const int32_t* __restrict__ rows, int window_len,
+                                                            long n_variants, long S, float* __restrict__ hap1,
+                                                            float* __restrict__ hap2, float* __restrict__ gp,
+                                                            int64_t* __restrict__ mask_out) {
+  __shared__ float sp1[SC_B][SC_T + 1], sp2[SC_B][SC_T + 1];
+  __shared__ int64_t sm[SC_B][SC_T + 1];
+  const int tid = threadIdx.x, t0 = blockIdx.x * SC_T, b0 = blockIdx.y * SC_B;
+  {
+    const int tt = tid & (SC_T - 1), t = t0 + tt + 1;
+#pragma unroll
+    for (int i = 0; i < SC_B / 4; ++i) {
+      const int bb = (tid >> 6) + 4 * i, b = b0 + bb;
+      if (b < B && t <= window_len) {
+        const long m = (long)b * L + t;
+        const float2 a = reinterpret_cast<const float2*>(ph1)[m], c = reinterpret_cast<const float2*>(ph2)[m];
+        sp1[bb][tt] = post_p_alt(a.x, a.y);
+        sp2[bb][tt] = post_p_alt(c.x, c.y);
+        sm[bb][tt] = mask[m];
+      }
+    }
+  }
+  __syncthreads();
+  const int bb = tid & (SC_B - 1), b = b0 + bb;
+  if (b >= B) return;
+  const long s = rows[b], w = rows[B + b];
+  if (s < 0 || s >= S || w < 0) return;          // refused on the host already; never a stray store
+#pragma unroll
+  for (int i = 0; i < SC_T / 16; ++i) {
+    const int tt = (tid >> 4) + 16 * i;
+    const long row = w * window_len + t0 + tt;
+    if (t0 + tt < window_len && row < n_variants) {
+      const long o = row * S + s;
+      const float p1 = sp1[bb][tt], p2 = sp2[bb][tt];
+      hap1[o] = p1;
+      hap2[o] = p2;
+      reinterpret_cast<f32x4*>(gp)[o] = post_gt(p1, p2);
+      mask_out[o] = sm[bb][tt];
+    }
+  }
 }
 
 extern "C" int snvrag_infer_post(int64_t M, const float* probs_h1, const float* probs_h2, float* p1, float* p2,
@@ -456,6 +513,29 @@ extern "C" int snvrag_infer_post(int64_t M, const float* probs_h1, const float* 
   if (M == 0) return 0;
   hipLaunchKernelGGL(infer_post_kernel, dim3(cdiv(M, 256)), dim3(256), 0, as_stream(stream), (long)M, probs_h1,
                      probs_h2, p1, p2, gt);
+  SNV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int snvrag_infer_scatter(int64_t B, int32_t L, const float* probs_h1, const float* probs_h2,
+                                    const int64_t* mask, const int32_t* rows_dev, const int32_t* rows_host,
+                                    int32_t window_len, int64_t n_variants, int64_t S, float* hap1, float* hap2,
+                                    float* gp, int64_t* mask_out, void* stream) {
+  SNV_CHECK_ARG(probs_h1 && probs_h2 && mask && rows_dev && rows_host && hap1 && hap2 && gp && mask_out,
+                "null pointer");
+  SNV_CHECK_ARG(((uintptr_t)gp % 16) == 0 && ((uintptr_t)probs_h1 % 8) == 0 && ((uintptr_t)probs_h2 % 8) == 0,
+                "gp must be 16-byte, probs 8-byte aligned");
+  SNV_CHECK_ARG(L >= 2 && window_len >= 1 && window_len <= L - 1, "window_len must be in [1, L - 1]");
+  SNV_CHECK_ARG(B >= 0 && B * (int64_t)L < (1LL << 31), "B * L must be below 2^31");
+  SNV_CHECK_ARG(n_variants >= 0 && S >= 1, "n_variants >= 0 and S >= 1");
+  for (int64_t b = 0; b < B; ++b) {
+    SNV_CHECK_ARG(rows_host[b] >= 0 && rows_host[b] < S, "sample index out of range");
+    SNV_CHECK_ARG(rows_host[B + b] >= 0, "window index out of range");
+  }
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(infer_scatter_kernel, dim3(cdiv(window_len, SC_T), cdiv(B, SC_B)), dim3(256), 0,
+                     as_stream(stream), (int)B, (int)L, probs_h1, probs_h2, mask, rows_dev, (int)window_len,
+                     (long)n_variants, (long)S, hap1, hap2, gp, mask_out);
   SNV_LAUNCH_CHECK();
   return 0;
 }

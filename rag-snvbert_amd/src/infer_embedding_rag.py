@@ -62,6 +62,10 @@ def parse_args(argv=None):
     p.add_argument("--panel_codes", default="u8", choices=["u8", "bits"],
                    help="layout of the HBM panel index: one byte per site, or bit-packed (1/8 of the memory, "
                         "identical neighbours)")
+    p.add_argument("--device_features", action="store_true",
+                   help="build the batches on the GPU from device-resident tables (dataset/device_features.py) and, "
+                        "with one process, write the results straight into the site-major arrays; off by default, "
+                        "identical outputs (0/1 genotypes only)")
     p.add_argument("--seed", type=int, default=0, help="weight init without --check_point (synthetic runs)")
     p.add_argument("--dist_backend", default="nccl", choices=["nccl", "gloo"],
                    help="WORLD_SIZE > 1 (torch.distributed.run, one process per GPU): nccl (= RCCL) or gloo "
@@ -159,8 +163,11 @@ def _gather_rows(t: torch.Tensor, sizes, group=None) -> torch.Tensor:
     return torch.cat([g[r, :n] for r, n in enumerate(sizes)])
 
 
+OUTPUT_BUDGET_BYTES = 16 << 30      # device result arrays of the device_features output path
+
+
 def run(ds, model, dev, batch_size: int, k: int, num_workers: int = 0, window_len: int = INFER_WINDOW_LEN,
-        group=None):
+        group=None, device_features: bool = False, output_budget_bytes: int = OUTPUT_BUDGET_BYTES):
     """The inference loop (infer_embedding_rag.py:132-157) and geometry (:165-203) over ``ds``
     with an eval ``model`` on ``dev``.  Returns host arrays h1/h2 [n_sites, S], gt
     [n_sites, S, 4], mask [n_sites, S], the neighbour indices per sampler row and the time.
@@ -169,7 +176,15 @@ def run(ds, model, dev, batch_size: int, k: int, num_workers: int = 0, window_le
     rank r imputes rows ``rank_rows`` of the window-major stream (batches formed inside its
     slice), and the per-row outputs are all-gathered in stream order before the geometry — the
     same arrays as one process (every row's retrieval and forward depend on that row alone).
-    ``seconds`` is the slowest rank's loop time."""
+    ``seconds`` is the slowest rank's loop time.
+
+    ``device_features``: the batches come from ``DeviceBatchLoader`` (built on the GPU, same sampler
+    rows).  With one process the per-batch outputs also go through ``kernels.infer_scatter`` into
+    device result arrays [n_sites, S] (32 bytes per site and sample), copied to the host once — in
+    place of the concatenation and the host ``geometry``; the per-row ``batch_*`` entries are then
+    None.  If the arrays would exceed ``output_budget_bytes`` (default 16 GiB), or with several
+    ranks, the existing output path runs (with a printed note) and only the input side changes."""
+    from . import kernels as K
     from .dataset.embedding_rag_dataset import embedding_rag_collate_fn
     from .dataset.sampler import WindowMajorSampler
     import torch.distributed as dist
@@ -178,8 +193,25 @@ def run(ds, model, dev, batch_size: int, k: int, num_workers: int = 0, window_le
     emb = model.bert.embedding
     order = list(iter(WindowMajorSampler(ds)))
     lo, hi = rank_rows(len(order), rank, world)
-    loader = torch.utils.data.DataLoader(ds, batch_size=batch_size, sampler=order[lo:hi],
-                                         num_workers=num_workers, collate_fn=embedding_rag_collate_fn)
+    site = None                      # device result arrays of the scatter output path
+    if device_features:
+        from .dataset.device_features import DeviceBatchLoader
+        loader = DeviceBatchLoader(ds, order[lo:hi], batch_size, dev)
+        n_sites, S = len(ds.ori_pos), len(order) // max(ds.window_count, 1)
+        need = 32 * n_sites * S
+        if world > 1:
+            pass                     # ranks hold disjoint rows: the per-row gather and host geometry stay
+        elif need > output_budget_bytes:
+            print(f"device_features: site-major result arrays need {need} bytes > output_budget_bytes "
+                  f"{output_budget_bytes}; keeping the per-batch outputs and the host geometry", flush=True)
+        else:
+            site = dict(h1=torch.zeros(n_sites, S, device=dev), h2=torch.zeros(n_sites, S, device=dev),
+                        gt=torch.zeros(n_sites, S, 4, device=dev),
+                        mask=torch.zeros(n_sites, S, device=dev, dtype=torch.long))
+            masked = torch.zeros((), device=dev, dtype=torch.long)
+    else:
+        loader = torch.utils.data.DataLoader(ds, batch_size=batch_size, sampler=order[lo:hi],
+                                             num_workers=num_workers, collate_fn=embedding_rag_collate_fn)
     outs = {"h1": [], "h2": [], "gt": [], "mask": [], "idx1": [], "idx2": []}
     t0 = time.perf_counter()
     with torch.no_grad():
@@ -187,15 +219,28 @@ def run(ds, model, dev, batch_size: int, k: int, num_workers: int = 0, window_le
             batch = ds.process_batch_retrieval(batch, emb, dev, k)
             x = {key: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for key, v in batch.items()}
             out = model(x)
-            p1, p2, gt = postprocess(out[0], out[1])
-            outs["h1"].append(p1)
-            outs["h2"].append(p2)
-            outs["gt"].append(gt)
-            outs["mask"].append(x["mask"])
+            if site is not None:
+                K.infer_scatter(out[0].float().contiguous(), out[1].float().contiguous(), x["mask"], batch.rows_dev,
+                                batch.rows_host, min(window_len, MAX_SEQ_LEN - 1), site["h1"], site["h2"],
+                                site["gt"], site["mask"])
+                masked += x["mask"].sum()
+            else:
+                p1, p2, gt = postprocess(out[0], out[1])
+                outs["h1"].append(p1)
+                outs["h2"].append(p2)
+                outs["gt"].append(gt)
+                outs["mask"].append(x["mask"])
             outs["idx1"].append(x["rag_idx_h1"])
             outs["idx2"].append(x["rag_idx_h2"])
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if site is not None:
+        host = {key: v.cpu().numpy() for key, v in site.items()}
+        for key in ("idx1", "idx2"):
+            host[key] = torch.cat(outs[key]).cpu().numpy()
+        return dict(h1=host["h1"], h2=host["h2"], gt=host["gt"], mask=host["mask"], idx1=host["idx1"],
+                    idx2=host["idx2"], seconds=elapsed, masked_snvs=int(masked.item()) * 2, batch_mask=None,
+                    batch_h1=None, batch_h2=None)
     if world > 1:
         sizes = [rank_rows(len(order), r, world)[1] - rank_rows(len(order), r, world)[0] for r in range(world)]
         full = {}
@@ -254,7 +299,8 @@ def infer(argv=None):
         model.load_state_dict(sd, strict=True)
     model = model.to(dev).eval()
     engine_for(model).set_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
-    res = run(ds, model, dev, args.infer_batch_size, args.k_retrieve, args.num_workers, args.window_len)
+    res = run(ds, model, dev, args.infer_batch_size, args.k_retrieve, args.num_workers, args.window_len,
+              device_features=args.device_features)
     h1, h2, gt, mask = res["h1"], res["h2"], res["gt"], res["mask"]
     if rank != 0:                      # the gathered arrays are written once
         return res

@@ -693,6 +693,53 @@ def infer_post(probs_h1: torch.Tensor, probs_h2: torch.Tensor):
     return p1, p2, gt
 
 
+def _rows_host(rows_host: torch.Tensor, B: int) -> int:
+    assert not rows_host.is_cuda and rows_host.dtype == torch.int32 and rows_host.is_contiguous() and \
+        rows_host.numel() >= 3 * B
+    return int(rows_host.data_ptr())
+
+
+def infer_scatter(probs_h1: torch.Tensor, probs_h2: torch.Tensor, mask: torch.Tensor, rows_dev: torch.Tensor,
+                  rows_host: torch.Tensor, window_len: int, hap1: torch.Tensor, hap2: torch.Tensor, gp: torch.Tensor,
+                  mask_out: torch.Tensor) -> None:
+    """``infer_post`` of one batch written straight into the site-major result arrays of
+    infer_embedding_rag.geometry: hap1 / hap2 f32 [n_variants, S], gp f32 [n_variants, S, 4], mask_out
+    i64 [n_variants, S] (zeroed once by the caller).  ``rows_dev`` / ``rows_host``: the batch's int32
+    [3, B] row table (sample, window, flags) on the device and on the host."""
+    N.require_gpu(probs_h1, probs_h2, mask, rows_dev, hap1, hap2, gp, mask_out)
+    B, L = mask.shape
+    assert probs_h1.shape == (B, L, 2) and probs_h2.shape == (B, L, 2) and mask.dtype == torch.int64
+    assert probs_h1.dtype == torch.float32 and probs_h2.dtype == torch.float32
+    assert rows_dev.dtype == torch.int32 and rows_dev.numel() >= 3 * B
+    n_variants, S = hap1.shape
+    assert hap2.shape == (n_variants, S) and gp.shape == (n_variants, S, 4) and mask_out.shape == (n_variants, S)
+    assert hap1.dtype == hap2.dtype == gp.dtype == torch.float32 and mask_out.dtype == torch.int64
+    check(N.lib().snvrag_infer_scatter(B, L, ptr(_c(probs_h1)), ptr(_c(probs_h2)), ptr(_c(mask)), ptr(_c(rows_dev)),
+                                       _rows_host(rows_host, B), window_len, n_variants, S, ptr(_c(hap1)),
+                                       ptr(_c(hap2)), ptr(_c(gp)), ptr(_c(mask_out)), stream_ptr()), "infer_scatter")
+
+
+def batch_features(tables: "N.FeatureTables", rows_dev: torch.Tensor, rows_host: torch.Tensor, B: int, L: int,
+                   token_ids: Sequence[int], labels: bool = False):
+    """One launch builds a batch from the device-resident tables (``dataset.device_features``):
+    returns tokens i64 [2B, L] (hap_1 rows, then hap_2 rows), mask i64 [B, L], floats f32 [6, B, L]
+    (pos, af, af_p, ref, het, hom) and labels i64 [3, B, L] (hap_1_label, hap_2_label, gt_label) or
+    None.  ``rows_dev`` / ``rows_host``: int32 [3, B] (sample, window, flags) on the device and on the
+    host; ``token_ids`` = (sos, eos, pad, mask, tok0, tok1)."""
+    N.require_gpu(rows_dev)
+    assert rows_dev.dtype == torch.int32 and rows_dev.is_contiguous() and rows_dev.numel() >= 3 * B
+    dev = rows_dev.device
+    tokens = torch.empty(2 * B, L, device=dev, dtype=torch.int64)
+    mask = torch.empty(B, L, device=dev, dtype=torch.int64)
+    floats = torch.empty(6, B, L, device=dev, dtype=torch.float32)
+    lab = torch.empty(3, B, L, device=dev, dtype=torch.int64) if labels else None
+    sos, eos, pad, msk, tok0, tok1 = (int(v) for v in token_ids)
+    check(N.lib().snvrag_batch_features(C.byref(tables), ptr(rows_dev), _rows_host(rows_host, B), B, L, sos, eos, pad,
+                                        msk, tok0, tok1, ptr(tokens), ptr(mask), ptr(floats), ptr(lab), stream_ptr()),
+          "batch_features")
+    return tokens, mask, floats, lab
+
+
 def ln_fwd_train(x: torch.Tensor, r: Optional[torch.Tensor], g: torch.Tensor, b: torch.Tensor, eps: float,
                  p_r: float = 0.0, p_out: float = 0.0, seed: int = 0, slope_x: float = 0.0, slope_r: float = 0.0):
     """(y bf16, s bf16 = act_x(x) + drop(act_r(r)) (x itself when r is None), stats f32 [M, 2]); y

@@ -22,7 +22,7 @@ LIB_PATH = Path(os.environ.get("SNVRAG_LIB", PKG_DIR / "lib" / "libsnvrag.so"))
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_LRELU, ACT_SIGMOID = 0, 1, 2, 3
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 vp, i64, i32, f32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
 
@@ -71,6 +71,13 @@ class GtW(C.Structure):
 class AdamS(C.Structure):
     _fields_ = [("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32),
                 ("grad_scale", f32), ("max_norm", f32), ("step", C.c_int)]
+
+
+class FeatureTables(C.Structure):
+    _fields_ = [(n, vp) for n in ("gt_bits", "win_off", "site_row", "freq_col", "pos_norm", "win_mask", "freq",
+                                  "pop_of_sample")] + \
+               [("ld_bits", i64), ("n_cols", i64), ("n_samples", i32), ("n_windows", i32), ("max_window_sites", i32),
+                ("n_pop", i32), ("global_row", i32)]
 
 
 class LayerW(C.Structure):
@@ -154,6 +161,9 @@ _SIGS = {
     "snvrag_adam_step": ([i64, vp, vp, vp, vp, vp, vp, C.POINTER(AdamS), vp], C.c_int),
     "snvrag_confusion": ([i64, C.c_int, vp, vp, vp, vp, vp, vp], C.c_int),
     "snvrag_infer_post": ([i64, vp, vp, vp, vp, vp, vp], C.c_int),
+    "snvrag_infer_scatter": ([i64, i32, vp, vp, vp, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp], C.c_int),
+    "snvrag_batch_features": ([C.POINTER(FeatureTables), vp, vp, i64, i32, C.c_int, C.c_int, C.c_int, C.c_int,
+                               C.c_int, C.c_int, vp, vp, vp, vp, vp], C.c_int),
     "snvrag_mlp_pack_bytes": ([C.c_int], sz),
     "snvrag_mlp_pack": ([C.c_int, vp, vp, vp, vp], C.c_int),
     "snvrag_mlp_forward": ([i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, f32, vp, vp], C.c_int),

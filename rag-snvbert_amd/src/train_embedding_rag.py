@@ -5,7 +5,8 @@ model and optimiser hyper-parameters, rag_k, resume, output) plus:
   --synthetic N_SAMPLES   build the data in memory (src/dataset/synthetic.py) — this image
                           has no 1000-Genomes files and no h5py/allel to read them;
   --max_steps N           stop an epoch after N batches (smoke runs);
-  --deterministic         fixed-order reductions in the training step (two runs, one checkpoint).
+  --deterministic         fixed-order reductions in the training step (two runs, one checkpoint);
+  --device_features       batches built on the GPU from device-resident tables (same batches).
 Multi-GPU: launch one process per GPU with torch.distributed.run; ranks walk the windows
 in lock-step (DistributedWindowSampler), sum gradients with bucketed RCCL all-reduces
 (src/main/optimizer.py: the reference's DataParallel gradient over the global batch), sum
@@ -72,6 +73,9 @@ def parse_args(argv=None):
     p.add_argument("--deterministic", action="store_true",
                    help="fixed-order reductions in every training step (no float atomics): two runs of the same "
                         "command give the same checkpoint; no reference counterpart, off by default")
+    p.add_argument("--device_features", action="store_true",
+                   help="build the batches on the GPU from device-resident tables (dataset/device_features.py: "
+                        "DeviceBatchLoader over the same samplers); off by default, identical batches")
     return p.parse_args(argv)
 
 
@@ -98,9 +102,13 @@ def build_data(args, rank: int, world: int):
     else:
         raise SystemExit("reading the reference's H5/VCF inputs needs h5py and scikit-allel, which this image "
                          "does not have; run with --synthetic N (in-memory data with the same file contract)")
-    mk = lambda ds, sampler, bs: torch.utils.data.DataLoader(ds, batch_size=bs, sampler=sampler,
-                                                             num_workers=args.num_workers,
-                                                             collate_fn=embedding_rag_collate_fn)
+    if getattr(args, "device_features", False):
+        from .dataset.device_features import DeviceBatchLoader
+        mk = lambda ds, sampler, bs: DeviceBatchLoader(ds, sampler, bs, torch.device("cuda", torch.cuda.current_device()))
+    else:
+        mk = lambda ds, sampler, bs: torch.utils.data.DataLoader(ds, batch_size=bs, sampler=sampler,
+                                                                 num_workers=args.num_workers,
+                                                                 collate_fn=embedding_rag_collate_fn)
     # train_embedding_rag.py:218, :260 — seed 42 for the train order, deterministic validation
     if world > 1:
         ts = DistributedWindowSampler(train, rank, world, shuffle=True, seed=42)
