@@ -718,6 +718,29 @@ int snvrag_batch_features(const snvrag_feature_tables_t* tables, const int32_t* 
                           int tok0, int tok1, int64_t* tokens, int64_t* mask_out, float* floats, int64_t* labels,
                           void* stream);
 
+/* Device VCF writer (opt-in; the text src/dataset/utils.py:378-479 generate_vcf_efficient_optimized lays
+ * out, byte for byte what write_vcf / vcf_cells of this package write, infer_embedding_rag.py:97-128):
+ * formats one chunk of n_lines records into the device text buffer out [out_bytes].
+ *   h1, h2       f32 [n][S], gt f32 [n][S][4] (16-byte aligned): the site-major result arrays;
+ *   rows         i32 [n_lines]: the site row of each line, in [0, n);
+ *   line_off     i64 [n_lines + 1]: byte offsets of the lines in out, monotone, line_off[n_lines] <= out_bytes;
+ *   prefix_off   i32 [n_lines + 1]: offsets into prefix_blob [prefix_bytes], the host-built line prefixes
+ *                (CHROM .. FORMAT and the tab behind it).
+ * Line i = prefix i, then S cells "G:h1,h2:gp0,gp1,gp2:ds" of 39 bytes, each followed by a tab, the last
+ * by a newline: line_off[i + 1] - line_off[i] = len(prefix i) + 40 S (the caller's contract; a line
+ * that breaks it, or a row outside [0, n), is left unwritten and counted in bad_count).
+ * G = "0|0" "0|1" "1|0" "1|1"[first argmax of gt]; gp0 = gt[0], gp1 = gt[1] + gt[2], gp2 = gt[3],
+ * ds = gp1 + 2 gp2 in f32; every number '%.3f' of the exact binary value, round-half-even, in integer
+ * arithmetic.  A value that is NaN, infinite, has the sign bit set (-0.0 too) or rounds to >= 10.000
+ * does not fit the fixed width: it adds 1 to *bad_count (device i32, zeroed by the caller) and the
+ * caller discards the text.  All pointers are device pointers; out is 16-byte aligned.
+ * Refused: a null pointer, S < 1, n < 1, out_bytes or prefix_bytes >= 2^31, n_lines * 40 S > out_bytes,
+ * a misaligned out or gt. */
+int snvrag_vcf_format(int64_t n, int64_t S, const float* h1, const float* h2, const float* gt,
+                      int64_t n_lines, const int32_t* rows, const int64_t* line_off, const int32_t* prefix_off,
+                      const uint8_t* prefix_blob, int64_t prefix_bytes, uint8_t* out, int64_t out_bytes,
+                      int32_t* bad_count, void* stream);
+
 /* self tests of MFMA operand/accumulator layouts used by the kernels (GPU only):
  * returns 0 when the i8 / bf16 / f32 MFMA maps match the CPU product. */
 int snvrag_selftest_mfma(void* stream);

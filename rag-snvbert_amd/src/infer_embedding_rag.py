@@ -13,7 +13,8 @@ Outputs (``--output_path``): ``imputed.npz`` (hap1/hap2 ALT probabilities, GP, m
 positions) and ``imputed.vcf`` (the imputed sites = mask of the first sample, as
 infer_embedding_rag.py:237; GT phased argmax, HDS, GP = (p00, p01 + p10, p11), DS,
 ``%.3f``).  The reference's VCF call fails with a TypeError, so the
-writer here defines the output instead of mirroring it.
+writer here defines the output instead of mirroring it.  ``--vcf_writer device`` writes the same
+file, byte for byte, with the records formatted on the GPU (vcf_device.py, csrc/vcf.hip).
 
 Windows: query windows are INFER_WINDOW_LEN = 1020 sites; ``--index_window_len`` 510
 (default) reproduces the reference's 510-site index windows and infer masks
@@ -59,6 +60,9 @@ def parse_args(argv=None):
     p.add_argument("--mask_rate", type=float, default=0.3,
                    help="synthetic: fraction of panel sites absent from the target (C5 sweep 0.1..0.9)")
     p.add_argument("--no_vcf", action="store_true")
+    p.add_argument("--vcf_writer", default="host", choices=["host", "device"],
+                   help="host: the Python writer; device: the records formatted on the GPU (vcf_device.py), the same "
+                        "file byte for byte")
     p.add_argument("--panel_codes", default="u8", choices=["u8", "bits"],
                    help="layout of the HBM panel index: one byte per site, or bit-packed (1/8 of the memory, "
                         "identical neighbours)")
@@ -128,6 +132,9 @@ def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, al
                     "\t".join(vcf_cells(h1[i], h2[i], gt[i])) + "\n")
 
 
+from .vcf_device import milli_f32, write_vcf_device  # noqa: E402  (the opt-in device writer of the same file)
+
+
 def build_dataset(args):
     from .dataset.embedding_rag_infer_dataset import EmbeddingRAGInferDataset
     from .dataset.vocab import WordVocab
@@ -167,7 +174,8 @@ OUTPUT_BUDGET_BYTES = 16 << 30      # device result arrays of the device_feature
 
 
 def run(ds, model, dev, batch_size: int, k: int, num_workers: int = 0, window_len: int = INFER_WINDOW_LEN,
-        group=None, device_features: bool = False, output_budget_bytes: int = OUTPUT_BUDGET_BYTES):
+        group=None, device_features: bool = False, output_budget_bytes: int = OUTPUT_BUDGET_BYTES,
+        keep_site_dev: bool = False):
     """The inference loop (infer_embedding_rag.py:132-157) and geometry (:165-203) over ``ds``
     with an eval ``model`` on ``dev``.  Returns host arrays h1/h2 [n_sites, S], gt
     [n_sites, S, 4], mask [n_sites, S], the neighbour indices per sampler row and the time.
@@ -183,7 +191,9 @@ def run(ds, model, dev, batch_size: int, k: int, num_workers: int = 0, window_le
     device result arrays [n_sites, S] (32 bytes per site and sample), copied to the host once — in
     place of the concatenation and the host ``geometry``; the per-row ``batch_*`` entries are then
     None.  If the arrays would exceed ``output_budget_bytes`` (default 16 GiB), or with several
-    ranks, the existing output path runs (with a printed note) and only the input side changes."""
+    ranks, the existing output path runs (with a printed note) and only the input side changes.
+    ``keep_site_dev``: when that scatter path ran, the device arrays h1 / h2 / gt are also returned under
+    ``site_dev`` (for ``write_vcf_device``, which formats from them in place); the caller frees them."""
     from . import kernels as K
     from .dataset.embedding_rag_dataset import embedding_rag_collate_fn
     from .dataset.sampler import WindowMajorSampler
@@ -238,9 +248,12 @@ def run(ds, model, dev, batch_size: int, k: int, num_workers: int = 0, window_le
         host = {key: v.cpu().numpy() for key, v in site.items()}
         for key in ("idx1", "idx2"):
             host[key] = torch.cat(outs[key]).cpu().numpy()
-        return dict(h1=host["h1"], h2=host["h2"], gt=host["gt"], mask=host["mask"], idx1=host["idx1"],
-                    idx2=host["idx2"], seconds=elapsed, masked_snvs=int(masked.item()) * 2, batch_mask=None,
-                    batch_h1=None, batch_h2=None)
+        res = dict(h1=host["h1"], h2=host["h2"], gt=host["gt"], mask=host["mask"], idx1=host["idx1"],
+                   idx2=host["idx2"], seconds=elapsed, masked_snvs=int(masked.item()) * 2, batch_mask=None,
+                   batch_h1=None, batch_h2=None)
+        if keep_site_dev:
+            res["site_dev"] = dict(h1=site["h1"], h2=site["h2"], gt=site["gt"])
+        return res
     if world > 1:
         sizes = [rank_rows(len(order), r, world)[1] - rank_rows(len(order), r, world)[0] for r in range(world)]
         full = {}
@@ -300,8 +313,10 @@ def infer(argv=None):
     model = model.to(dev).eval()
     engine_for(model).set_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     res = run(ds, model, dev, args.infer_batch_size, args.k_retrieve, args.num_workers, args.window_len,
-              device_features=args.device_features)
+              device_features=args.device_features,
+              keep_site_dev=args.vcf_writer == "device" and not args.no_vcf)
     h1, h2, gt, mask = res["h1"], res["h2"], res["gt"], res["mask"]
+    site_dev = res.pop("site_dev", None)
     if rank != 0:                      # the gathered arrays are written once
         return res
     os.makedirs(args.output_path, exist_ok=True)
@@ -309,8 +324,16 @@ def infer(argv=None):
                         pos=np.asarray(ds.ori_pos))
     if not args.no_vcf:
         samples = [f"S{i}" for i in range(h1.shape[1])]
-        write_vcf(os.path.join(args.output_path, "imputed.vcf"), args.chrom, ds.ori_pos, h1, h2, gt, samples,
-                  pos_flag=mask[:, 0].astype(bool))
+        vcf_path, flag = os.path.join(args.output_path, "imputed.vcf"), mask[:, 0].astype(bool)
+        if args.vcf_writer == "device":
+            # in place from the scatter path's device arrays when there are any, else the host arrays
+            # (several ranks: the gathered ones) uploaded chunk by chunk
+            src = site_dev if site_dev is not None else dict(h1=h1, h2=h2, gt=gt)
+            write_vcf_device(vcf_path, args.chrom, ds.ori_pos, src["h1"], src["h2"], src["gt"], samples,
+                             pos_flag=flag, device=dev)
+            src = site_dev = None      # the device result arrays are freed after the write
+        else:
+            write_vcf(vcf_path, args.chrom, ds.ori_pos, h1, h2, gt, samples, pos_flag=flag)
     print(f"imputed {len(ds)} sample-windows in {res['seconds']:.2f}s "
           f"({res['masked_snvs'] / res['seconds']:.0f} masked SNVs/s)", flush=True)
     return res

@@ -740,6 +740,29 @@ def batch_features(tables: "N.FeatureTables", rows_dev: torch.Tensor, rows_host:
     return tokens, mask, floats, lab
 
 
+def vcf_format(h1: torch.Tensor, h2: torch.Tensor, gt: torch.Tensor, rows: torch.Tensor, line_off: torch.Tensor,
+               prefix_off: torch.Tensor, prefix_blob: torch.Tensor, out: torch.Tensor, out_bytes: int,
+               bad_count: torch.Tensor) -> None:
+    """The text of one chunk of VCF records (``vcf_device.write_vcf_device``): line i = prefix i followed by
+    the S cells of site row ``rows[i]`` of h1 / h2 f32 [n, S], gt f32 [n, S, 4], at ``out[line_off[i]:]``.
+    rows i32 [n_lines], line_off i64 [n_lines + 1], prefix_off i32 [n_lines + 1] into prefix_blob u8; out u8
+    with at least ``out_bytes`` bytes; bad_count i32 [1] += the values that do not print as d.ddd."""
+    N.require_gpu(h1, h2, gt, rows, line_off, prefix_off, prefix_blob, out, bad_count)
+    n, S = h1.shape
+    n_lines = rows.numel()
+    assert h2.shape == (n, S) and gt.shape == (n, S, 4)
+    assert h1.dtype == h2.dtype == gt.dtype == torch.float32
+    assert h1.is_contiguous() and h2.is_contiguous() and gt.is_contiguous()
+    assert rows.dtype == torch.int32 and prefix_off.dtype == torch.int32 and line_off.dtype == torch.int64
+    assert rows.is_contiguous() and line_off.is_contiguous() and prefix_off.is_contiguous()
+    assert line_off.numel() == n_lines + 1 and prefix_off.numel() == n_lines + 1
+    assert prefix_blob.dtype == torch.uint8 and out.dtype == torch.uint8 and bad_count.dtype == torch.int32
+    assert prefix_blob.is_contiguous() and out.is_contiguous() and 0 <= out_bytes <= out.numel()
+    check(N.lib().snvrag_vcf_format(n, S, ptr(h1), ptr(h2), ptr(gt), n_lines, ptr(rows), ptr(line_off),
+                                    ptr(prefix_off), ptr(prefix_blob), prefix_blob.numel(), ptr(out), out_bytes,
+                                    ptr(bad_count), stream_ptr()), "vcf_format")
+
+
 def ln_fwd_train(x: torch.Tensor, r: Optional[torch.Tensor], g: torch.Tensor, b: torch.Tensor, eps: float,
                  p_r: float = 0.0, p_out: float = 0.0, seed: int = 0, slope_x: float = 0.0, slope_r: float = 0.0):
     """(y bf16, s bf16 = act_x(x) + drop(act_r(r)) (x itself when r is None), stats f32 [M, 2]); y

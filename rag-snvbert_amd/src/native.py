@@ -164,6 +164,7 @@ _SIGS = {
     "snvrag_infer_scatter": ([i64, i32, vp, vp, vp, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp], C.c_int),
     "snvrag_batch_features": ([C.POINTER(FeatureTables), vp, vp, i64, i32, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_int, C.c_int, vp, vp, vp, vp, vp], C.c_int),
+    "snvrag_vcf_format": ([i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp], C.c_int),
     "snvrag_mlp_pack_bytes": ([C.c_int], sz),
     "snvrag_mlp_pack": ([C.c_int, vp, vp, vp, vp], C.c_int),
     "snvrag_mlp_forward": ([i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, f32, vp, vp], C.c_int),
