@@ -741,6 +741,57 @@ int snvrag_vcf_format(int64_t n, int64_t S, const float* h1, const float* h2, co
                       const uint8_t* prefix_blob, int64_t prefix_bytes, uint8_t* out, int64_t out_bytes,
                       int32_t* bad_count, void* stream);
 
+/* Device VCF reader (src/dataset/vcf_reader.py; what allel.read_vcf(fields=['variants/POS', 'calldata/GT'])
+ * gives the reference, embedding_rag_dataset.py:463-484, embedding_rag_infer_dataset.py:56-69): the body of a
+ * VCF parsed on the GPU into the bit rows of snvrag_feature_tables_t.gt_bits and of the packed panel index.
+ * text u8: a chunk that starts at a line start, nbytes in [1, 2^31) bytes, 16-byte aligned and padded by
+ * the caller with '\n' to a multiple of 16 bytes.  No kernel reads at or past the padded end.  All outputs
+ * are plain stores in a fixed order (no atomics).  All pointers are device pointers.
+ *
+ * snvrag_vcf_line_index: line_off i64 [max_lines + 1], sorted: the offsets of the lines of non-zero length
+ *   (a position whose predecessor is '\n' or the chunk start and where neither "\n" nor "\r\n" stands), then nbytes;
+ *   *n_lines (device i64) = their number, which may exceed max_lines: offsets past max_lines are dropped.
+ *   ws: snvrag_vcf_line_index_ws_bytes(nbytes), 16-byte aligned.
+ * snvrag_vcf_parse_gt: per line i, pos i32 [n_lines] = column 2 as decimal (0 when flagged) and
+ *   flags u32 [n_lines]:
+ *     bit 0   FORMAT (column 9) is absent or does not begin with GT followed by ':' or the column's end;
+ *     bit 1   the number of sample columns differs from S;
+ *     bit 2   a cell has more than two alleles;
+ *     bit 3   POS is absent, is not 1-10 decimal digits, or is >= 2^31;
+ *     bit 4   a cell's GT subfield is not allele (sep allele)*, allele = digits or '.', sep = '|' or '/'
+ *             (a byte that is none of digit . | /, an empty subfield, an empty allele);
+ *     bits 8-12   the OR of the line's codes (any ALT, any missing call, any '/');
+ *     bit 31  line_off[i] lies outside [0, nbytes).
+ *   codes u8 [n_lines][ld_codes], one byte per sample: bit 0 / bit 1 haplotype 1 / 2 carries an ALT allele
+ *   (allele number > 0), bit 2 / bit 3 haplotype 1 / 2 is missing ('.', or the absent second allele of a
+ *   haploid call), bit 4 the separator was '/'.  Only the first ':'-delimited subfield of a cell is read;
+ *   a '\r' in front of the newline is not part of the last cell.  Lines of the fixed-width form (after the
+ *   ninth tab exactly 4 S - 1 bytes of [0-9.][|/][0-9.] cells) take the coalesced path; any other line is
+ *   redone whole by the general path, with bitwise-equal outputs; force_general != 0 sends every line there.
+ *   ld_codes % 4 == 0; ws: snvrag_vcf_parse_ws_bytes(n_lines, S), 16-byte aligned.
+ * snvrag_vcf_pack_rows: codes -> alt_bits, miss_bits u8 [2 S][ld_bits]: haplotype h of sample s in row
+ *   2 s + h, record i at site site0 + i = bit (site & 7) of byte (site >> 3); an ALT bit is 0 where the call
+ *   is missing.  site0 % 64 == 0, ld_bits % 8 == 0; a last group of fewer than 64 records writes only
+ *   ceil(n / 8) bytes, with zero bits above the last record.
+ * snvrag_panel_gather_bits: out u8 [N][n_sites_pad / 8] (packed) or [N][n_sites_pad] (0/1 bytes) = sites
+ *   site_idx[0 .. n) of the bit rows bits [N][ld_bits] (n_src_sites sites each); a site_idx outside
+ *   [0, n_src_sites) (-1) and the padding sites n .. n_sites_pad give 0.
+ * snvrag_vcf_unpack_gt: gt i8 [n_sites][S][2] = 0 / 1 from alt_bits, -1 where miss_bits is set. */
+size_t snvrag_vcf_line_index_ws_bytes(int64_t nbytes);
+int snvrag_vcf_line_index(const uint8_t* text, int64_t nbytes, int64_t max_lines, int64_t* line_off,
+                          int64_t* n_lines, void* ws, size_t ws_bytes, void* stream);
+size_t snvrag_vcf_parse_ws_bytes(int64_t n_lines, int64_t S);
+int snvrag_vcf_parse_gt(const uint8_t* text, int64_t nbytes, const int64_t* line_off, int64_t n_lines,
+                        int64_t S, int force_general, int32_t* pos, uint32_t* flags, uint8_t* codes,
+                        int64_t ld_codes, void* ws, size_t ws_bytes, void* stream);
+int snvrag_vcf_pack_rows(const uint8_t* codes, int64_t ld_codes, int64_t n_lines, int64_t S, int64_t site0,
+                         uint8_t* alt_bits, uint8_t* miss_bits, int64_t ld_bits, void* stream);
+int snvrag_panel_gather_bits(const uint8_t* bits, int64_t N, int64_t ld_bits, int64_t n_src_sites,
+                             const int32_t* site_idx, int64_t n, int64_t n_sites_pad, int packed, uint8_t* out,
+                             void* stream);
+int snvrag_vcf_unpack_gt(const uint8_t* alt_bits, const uint8_t* miss_bits, int64_t ld_bits, int64_t S,
+                         int64_t n_sites, int8_t* gt, void* stream);
+
 /* self tests of MFMA operand/accumulator layouts used by the kernels (GPU only):
  * returns 0 when the i8 / bf16 / f32 MFMA maps match the CPU product. */
 int snvrag_selftest_mfma(void* stream);

@@ -3,8 +3,9 @@
 Same item contract as ``TrainDataset.__getitem__`` (dataset.py:455-582) and the
 v18 override (embedding_rag_dataset.py:486-555), vectorised: the reference's
 per-site Python loops over ``pos_to_idx`` become one numpy gather per field
-(SURVEY.md §8f row 1).  Files: ``from_file`` needs h5py (absent in this image →
-loud error); ``from_arrays`` takes the same data in memory.
+(SURVEY.md §8f row 1).  Files: ``from_file`` reads ``.vcf`` / ``.vcf.gz`` through the
+device reader (``vcf_reader.read_vcf``) and H5 through h5py (an optional dependency: a
+loud error without it); ``from_arrays`` takes the same data in memory.
 """
 
 from __future__ import annotations
@@ -52,6 +53,7 @@ class Window:
 class TrainDataset(torch.utils.data.Dataset):
     long_fields = ["hap_1", "hap_2", "hap_1_label", "hap_2_label", "gt_label", "mask", "hap1_nomask", "hap2_nomask"]
     float_fields = ["pos", "af", "af_p", "ref", "het", "hom"]
+    vcf_genotypes = None        # the VcfGenotypes behind ``vcf`` when it was read from a VCF file (device bit rows)
 
     def __init__(self, vocab: WordVocab, vcf: np.ndarray, pos: np.ndarray, panel: PanelData, freq: np.ndarray,
                  window: Window, type_to_idx: Dict, pop_to_idx: Dict, pos_to_idx: Dict):
@@ -137,29 +139,46 @@ class TrainDataset(torch.utils.data.Dataset):
 
     @classmethod
     def from_file(cls, vocab, vcfpath, panelpath, freqpath, windowpath, typepath, poppath, pospath):
-        gt, pos, t2i, p2i, pos2i = _read_inputs(vcfpath, typepath, poppath, pospath)
-        return cls(vocab, gt, pos, PanelData.from_file(panelpath), np.load(freqpath),
-                   Window.from_file(windowpath), t2i, p2i, pos2i)
+        gt, pos, t2i, p2i, pos2i, vg = _read_inputs_vcf(vcfpath, typepath, poppath, pospath)
+        ds = cls(vocab, gt, pos, PanelData.from_file(panelpath), np.load(freqpath),
+                 Window.from_file(windowpath), t2i, p2i, pos2i)
+        ds.vcf_genotypes = vg
+        return ds
 
 
 def _read_inputs(vcfpath, typepath, poppath, pospath):
     """GT (ALT > 0 -> 1), POS and the three mapping pickles (dataset.py:190-230, :747-771).
     The pickles are the reference's own mapping files, opened as the reference does."""
+    return _read_inputs_vcf(vcfpath, typepath, poppath, pospath)[:5]
+
+
+def read_genotypes(path, gt_key: str = "calldata/GT"):
+    """(gt, pos, VcfGenotypes or None) of a genotype file: ``.vcf`` / ``.vcf.gz`` through the device
+    reader (``vcf_reader.read_vcf``: the bit rows stay on the device beside the host array), anything
+    else as the reference's H5 (needs h5py)."""
+    from .vcf_reader import is_vcf_path, read_vcf
+    if is_vcf_path(path):
+        vg = read_vcf(path, torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cuda")
+        return vg.gt(), vg.pos, vg
     try:
         import h5py
     except ImportError as e:
-        raise RuntimeError("reading the VCF/H5 inputs needs h5py (not installed here); "
+        raise RuntimeError("reading H5 inputs needs h5py (not installed here); pass a .vcf / .vcf.gz file or "
                            "use from_arrays with in-memory GT/POS") from e
+    with h5py.File(path, "r") as f:
+        return f[gt_key][:], f["variants/POS"][:], None
+
+
+def _read_inputs_vcf(vcfpath, typepath, poppath, pospath):
+    """``_read_inputs`` and, last, the ``VcfGenotypes`` of a VCF input (None for H5)."""
     import pickle
-    with h5py.File(vcfpath, "r") as f:
-        gt = f["calldata/GT"][:]
-        pos = f["variants/POS"][:]
+    gt, pos, vg = read_genotypes(vcfpath)
     gt[gt > 0] = 1
     maps = []
     for path in (typepath, poppath, pospath):
         with open(path, "rb") as fh:
             maps.append(pickle.load(fh))
-    return (gt, pos, *maps)
+    return (gt, pos, *maps, vg)
 
 
 INFER_WINDOW_LEN = 1020     # dataset.py:26
@@ -234,5 +253,7 @@ class InferDataset(torch.utils.data.Dataset):
 
     @classmethod
     def from_file(cls, vocab, vcfpath, panelpath, freqpath, typepath, poppath, pospath):
-        gt, pos, t2i, p2i, pos2i = _read_inputs(vcfpath, typepath, poppath, pospath)
-        return cls(vocab, gt, pos, PanelData.from_file(panelpath), np.load(freqpath), t2i, p2i, pos2i)
+        gt, pos, t2i, p2i, pos2i, vg = _read_inputs_vcf(vcfpath, typepath, poppath, pospath)
+        ds = cls(vocab, gt, pos, PanelData.from_file(panelpath), np.load(freqpath), t2i, p2i, pos2i)
+        ds.vcf_genotypes = vg
+        return ds

@@ -25,7 +25,8 @@ Memory (``DeviceFeatures.nbytes`` = ``table_nbytes``):
 
 Not covered: genotype values other than 0/1 (missing = -1: ``ValueError``, those cohorts keep the
 host path); a plain ``TrainDataset`` (its masks draw from the global numpy RNG per item: nothing to
-reproduce); reading H5/VCF files.  Masks stay the host's numpy stream (``af_guided_mask``), so they
+reproduce); H5 files need h5py.  A dataset read from a VCF (``vcf_genotypes``, vcf_reader.py) hands its
+device bit rows over as ``gt_bits``: nothing is packed or uploaded again.  Masks stay the host's numpy stream (``af_guided_mask``), so they
 match the reference's seeds.
 """
 
@@ -108,17 +109,34 @@ def pack_genotypes(vcf: np.ndarray) -> np.ndarray:
     for s0 in range(0, S, step):
         g = vcf[:, s0:s0 + step]
         if ((g != 0) & (g != 1)).any():
-            raise ValueError("device features need 0/1 genotypes; this cohort holds other values (missing = -1?) "
-                             "and keeps the host path")
+            raise ValueError(MISSING_CALLS)
         if rows:
             g = np.ascontiguousarray(g.transpose(1, 2, 0)).reshape(-1, rows).astype(np.uint8)
             bits[2 * s0:2 * s0 + g.shape[0], :(rows + 7) // 8] = np.packbits(g, axis=1, bitorder="little")
     return bits
 
 
-def host_tables(ds, L: int = MAX_SEQ_LEN) -> Dict[str, np.ndarray]:
+MISSING_CALLS = ("device features need 0/1 genotypes; this cohort holds other values (missing = -1?) "
+                 "and keeps the host path")
+
+
+def vcf_gt_bits(ds):
+    """The device bit rows of a dataset read from a VCF (``ds.vcf_genotypes.alt_bits``: already the
+    ``gt_bits`` layout), or None.  Missing calls: the ``ValueError`` of ``pack_genotypes``."""
+    vg = getattr(ds, "vcf_genotypes", None)
+    if vg is None:
+        return None
+    if vg.any_missing:
+        raise ValueError(MISSING_CALLS)
+    n_rows, S = np.asarray(ds.vcf).shape[:2]
+    if vg.n_sites != n_rows or vg.alt_bits.shape != (2 * S, max(1, (n_rows + 7) // 8)):
+        return None                                            # the dataset no longer holds the file's rows
+    return vg.alt_bits
+
+
+def host_tables(ds, L: int = MAX_SEQ_LEN, gt_bits=None) -> Dict[str, np.ndarray]:
     """The static tables of ``ds`` on the host (module docstring), validated: every index the kernel
-    gathers with is in range."""
+    gathers with is in range.  ``gt_bits``: bit rows that exist already (a device tensor), taken as they are."""
     if not _is_infer(ds):
         if not isinstance(ds, TrainDataset) or not hasattr(ds, "window_actual_lens"):
             raise ValueError("device features need an EmbeddingRAGDataset (seeded per-window masks) or an infer "
@@ -135,7 +153,7 @@ def host_tables(ds, L: int = MAX_SEQ_LEN) -> Dict[str, np.ndarray]:
     freq = np.ascontiguousarray(ds.freq, np.float32)
     if freq.ndim != 3 or freq.shape[0] != 4 or freq.shape[1] <= GLOBAL:
         raise ValueError(f"frequency table must be [4, >= {GLOBAL + 1}, n_cols], got {freq.shape}")
-    t = dict(gt_bits=pack_genotypes(ds.vcf),
+    t = dict(gt_bits=pack_genotypes(ds.vcf) if gt_bits is None else gt_bits,
              win_off=np.concatenate([[0], np.cumsum(counts)]).astype(np.int32),
              site_row=np.concatenate([p[0] for p in parts]), freq_col=np.concatenate([p[1] for p in parts]),
              pos_norm=np.concatenate([p[2] for p in parts]), win_mask=window_masks(ds, L), freq=freq)
@@ -190,13 +208,14 @@ class DeviceFeatures:
         from .. import native as N
         self.dataset, self.device, self.L = dataset, torch.device(device), int(L)
         self.infer = _is_infer(dataset)
-        t = host_tables(dataset, self.L)
+        t = host_tables(dataset, self.L, vcf_gt_bits(dataset))
         self._mask_key = mask_key(dataset)
         self._mask_cache = {self._mask_key[:2] if self._mask_key else None: t["win_mask"]}
         self.win_off = t["win_off"].astype(np.int64)
         self.n_samples = int(t["pop_of_sample"].shape[0])
         self.n_items = len(dataset)
-        self.dev = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device) for k, v in t.items()}
+        self.dev = {k: (v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))).to(self.device)
+                    for k, v in t.items()}
         v = dataset.vocab
         self.token_ids = (v.sos_index, v.eos_index, v.pad_index, v.mask_index, v.stoi[0], v.stoi[1])
         T = N.FeatureTables()

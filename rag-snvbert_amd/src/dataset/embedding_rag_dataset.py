@@ -57,7 +57,8 @@ class EmbeddingRAGDataset(TrainDataset):
                  ref_gt: Optional[np.ndarray] = None, ref_pos: Optional[np.ndarray] = None,
                  embedding_layer=None, build_ref_data: bool = True, n_gpu: int = 1,
                  maf_mask_percentage: int = 10, use_dynamic_mask: bool = False, name: str = "default",
-                 index_cache_bytes: int = 64 << 30, panel_cache: str = "window", panel_codes: str = "u8"):
+                 index_cache_bytes: int = 64 << 30, panel_cache: str = "window", panel_codes: str = "u8",
+                 ref_vcf_path: Optional[str] = None):
         super().__init__(vocab, vcf, pos, panel, freq, window, type_to_idx, pop_to_idx, pos_to_idx)
         if panel_cache not in ("window", "fresh"):
             raise ValueError("panel_cache must be 'window' (the reference's per-window snapshot) or 'fresh'")
@@ -79,6 +80,11 @@ class EmbeddingRAGDataset(TrainDataset):
         self.embed_dim = embedding_layer.embed_size if embedding_layer is not None else None
         self._index_cache: "OrderedDict[int, object]" = OrderedDict()
         self._index_cache_bytes = index_cache_bytes
+        self.ref_panel_vcf = None                      # the panel's VcfGenotypes when it was read from a VCF
+        self.ref_site_rows: List[np.ndarray] = []      # panel rows of each window's matched sites
+        if ref_gt is None and ref_vcf_path is not None and build_ref_data:
+            ref_gt, ref_pos, self.ref_panel_vcf = load_ref_panel(ref_vcf_path)
+            ref_gt[ref_gt > 0] = 1
         if build_ref_data and ref_gt is not None:
             self._load_ref_data_to_memory(ref_gt, ref_pos)
 
@@ -108,6 +114,7 @@ class EmbeddingRAGDataset(TrainDataset):
             raw = self.generate_mask(n, probs=mask_probs(af, self._level))
             self.raw_window_masks.append(raw)
             self.window_masks.append(sequence_padding(raw, "int"))
+            self.ref_site_rows.append(ref_idx.astype(np.int32))
             alleles = np.asarray(ref_gt[ref_idx]).reshape(len(ref_idx), -1).T   # [n_haps, n]
             self.ref_alleles.append(alleles.astype(np.int64))
             self.ref_tokens_complete.append(self.tokenize(alleles, np.zeros(MAX_SEQ_LEN, np.int64)))
@@ -192,7 +199,8 @@ class EmbeddingRAGDataset(TrainDataset):
         idx = self._index_cache.get(w)
         if idx is None or idx.device != torch.device(device):
             idx = panel_index_of(self.ref_alleles[w], self.ref_af_windows[w], device, self.panel_shard,
-                                 self.panel_codes)
+                                 self.panel_codes, bit_rows_of(self.ref_panel_vcf, device),
+                                 self.ref_site_rows[w] if self.ref_site_rows else None)
             self._index_cache[w] = idx
             while sum(i.nbytes for i in self._index_cache.values()) > self._index_cache_bytes and \
                     len(self._index_cache) > 1:
@@ -205,6 +213,23 @@ class EmbeddingRAGDataset(TrainDataset):
     def process_batch_retrieval(self, batch: dict, embedding_layer, device, k_retrieve: int = 1,
                                 dense: bool = False, limbs: int = 2) -> dict:
         return retrieve(self, batch, embedding_layer, device, k_retrieve, self.window_masks, dense, limbs)
+
+    @staticmethod
+    def _load_ref_data(ref_vcf_path: str):
+        """embedding_rag_dataset.py:463-484 (VCF or H5 panel; no H5 side file is written)."""
+        return load_ref_panel(ref_vcf_path)[:2]
+
+    @classmethod
+    def from_file(cls, vocab, vcfpath, panelpath, freqpath, windowpath, typepath, poppath, pospath,
+                  ref_vcf_path=None, embedding_layer=None, build_ref_data=True, n_gpu=1, use_dynamic_mask=False,
+                  name="default", **kw) -> "EmbeddingRAGDataset":
+        """embedding_rag_dataset.py:557-606: the base dataset from its files, then the panel."""
+        base = TrainDataset.from_file(vocab, vcfpath, panelpath, freqpath, windowpath, typepath, poppath, pospath)
+        ds = cls(base.vocab, base.vcf, base.pos, base.panel, base.freq, base.window, base.type_to_idx,
+                 base.pop_to_idx, base.pos_to_idx, ref_vcf_path=ref_vcf_path, embedding_layer=embedding_layer,
+                 build_ref_data=build_ref_data, n_gpu=n_gpu, use_dynamic_mask=use_dynamic_mask, name=name, **kw)
+        ds.vcf_genotypes = base.vcf_genotypes
+        return ds
 
     @classmethod
     def from_arrays(cls, vocab, vcf, pos, pop_list, freq, window_bounds, pop_to_idx, pos_to_idx,
@@ -243,11 +268,35 @@ def check_panel_codes(panel_codes: str) -> str:
     return panel_codes
 
 
-def panel_index_of(alleles: np.ndarray, ref_af: np.ndarray, device, shard=None, panel_codes: str = "u8"):
+def load_ref_panel(path, h5_gt_key: str = "calldata/GT"):
+    """(gt [sites, samples, 2], pos, VcfGenotypes or None) of a reference panel file: ``.vcf`` / ``.vcf.gz``
+    through the device reader, anything else as H5."""
+    from .dataset import read_genotypes
+    return read_genotypes(path, h5_gt_key)
+
+
+def bit_rows_of(vg, device):
+    """The panel's haplotype bit rows on ``device`` when it came from ``read_vcf`` without missing calls
+    (a window's index is then gathered from them on the device), else None: the index is built from
+    the host alleles, which refuses missing calls."""
+    if vg is None or vg.any_missing or vg.alt_bits.device != torch.device(device):
+        return None
+    return vg
+
+
+def panel_index_of(alleles: np.ndarray, ref_af: np.ndarray, device, shard=None, panel_codes: str = "u8",
+                   bit_rows=None, site_rows: Optional[np.ndarray] = None):
     """PanelIndex of one window's panel, or of this rank's contiguous range of it; ``panel_codes``
-    "bits" builds the bit-packed layout (packed on the host, uploaded as bits)."""
+    "bits" builds the bit-packed layout (packed on the host, uploaded as bits).  ``bit_rows`` (a
+    ``VcfGenotypes``) with the window's panel rows ``site_rows``: gathered on the device from the
+    panel's bit rows instead (``PanelIndex.from_bit_rows``), the same index."""
     from ..retrieval import PanelIndex
     packed = check_panel_codes(panel_codes) == "bits"
+    if bit_rows is not None and site_rows is not None:
+        bits, n_hap = bit_rows.alt_bits, bit_rows.alt_bits.shape[0]
+        r0, r1 = (0, n_hap) if shard is None else shard.bounds(n_hap)
+        return PanelIndex.from_bit_rows(bits[r0:r1], site_rows, ref_af, packed=packed, ref_offset=r0, n_total=n_hap,
+                                        n_src_sites=bit_rows.n_sites)
     if shard is None:
         return PanelIndex.from_alleles(alleles, ref_af, device, packed=packed)
     r0, r1 = shard.bounds(alleles.shape[0])

@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from .dataset import INFER_WINDOW_LEN, InferDataset, PanelData
-from .embedding_rag_dataset import check_panel_codes, panel_index_of, retrieve
+from .embedding_rag_dataset import bit_rows_of, check_panel_codes, load_ref_panel, panel_index_of, retrieve
 from .utils import MAX_SEQ_LEN, sequence_padding
 
 REFERENCE_INDEX_WINDOW = 510     # embedding_rag_infer_dataset.py:16
@@ -64,8 +64,10 @@ class EmbeddingRAGInferDataset(InferDataset):
         self.jit_cache_win_idx = -1
         self._index_cache: "OrderedDict[int, object]" = OrderedDict()
         self._index_cache_bytes = index_cache_bytes
+        self.ref_panel_vcf = None                      # the panel's VcfGenotypes when it was read from a VCF
+        self.ref_site_rows: List[np.ndarray] = []      # panel rows of each index window's sites
         if ref_gt is None and ref_vcf_path is not None and build_ref_data and build_index:
-            ref_gt, ref_pos = self._load_ref_data(ref_vcf_path)
+            ref_gt, ref_pos, self.ref_panel_vcf = load_ref_panel(ref_vcf_path, "gt")
         if build_ref_data and build_index and ref_gt is not None:
             self._build_embedding_indexes(ref_gt, ref_pos)
 
@@ -73,13 +75,7 @@ class EmbeddingRAGInferDataset(InferDataset):
     @staticmethod
     def _load_ref_data(ref_vcf_path: str):
         """:56-69 (h5 or VCF panel)."""
-        try:
-            import h5py
-        except ImportError as e:
-            raise RuntimeError("reading the reference panel needs h5py (not installed here); "
-                               "pass ref_gt / ref_pos arrays") from e
-        with h5py.File(ref_vcf_path, "r") as f:
-            return f["gt"][:], f["variants/POS"][:]
+        return load_ref_panel(ref_vcf_path, "gt")[:2]
 
     def _build_embedding_indexes(self, ref_gt: np.ndarray, ref_pos: np.ndarray) -> None:
         """:71-207 without the embedding pass: per window, the infer mask (site absent from the
@@ -106,6 +102,7 @@ class EmbeddingRAGInferDataset(InferDataset):
                 raise ValueError(f"infer window {w}: none of its sites is in the reference panel")
             mask, cur, ref_rows = mask[keep], cur[keep], ref_rows[keep]
             self.index_sites.append(start + keep)
+            self.ref_site_rows.append(ref_rows.astype(np.int32))
             cols = np.array([self.pos_to_idx.get(p, -1) for p in cur.tolist()], dtype=np.int64)
             af = np.where(cols >= 0, self.freq[3][5][np.maximum(cols, 0)], 0.0).astype(np.float32)
             self.ref_af_windows.append(sequence_padding(af, "float").astype(np.float32))
@@ -130,7 +127,8 @@ class EmbeddingRAGInferDataset(InferDataset):
         idx = self._index_cache.get(w)
         if idx is None or idx.device != torch.device(device):
             idx = panel_index_of(self.ref_alleles[w], self.ref_af_windows[w], device, self.panel_shard,
-                                 self.panel_codes)
+                                 self.panel_codes, bit_rows_of(self.ref_panel_vcf, device),
+                                 self.ref_site_rows[w] if self.ref_site_rows else None)
             self._index_cache[w] = idx
             while sum(i.nbytes for i in self._index_cache.values()) > self._index_cache_bytes and \
                     len(self._index_cache) > 1:
@@ -163,9 +161,11 @@ class EmbeddingRAGInferDataset(InferDataset):
     def from_file(cls, vocab, vcfpath, panelpath, freqpath, typepath, poppath, pospath, ref_vcf_path=None,
                   embedding_layer=None, build_ref_data=True, n_gpu=1, name="infer", **kw):
         base = InferDataset.from_file(vocab, vcfpath, panelpath, freqpath, typepath, poppath, pospath)
-        return cls(vocab, base.vcf, base.pos, base.panel, base.freq, base.type_to_idx, base.pop_to_idx,
-                   base.pos_to_idx, ref_vcf_path=ref_vcf_path, embedding_layer=embedding_layer,
-                   build_ref_data=build_ref_data, n_gpu=n_gpu, name=name, **kw)
+        ds = cls(vocab, base.vcf, base.pos, base.panel, base.freq, base.type_to_idx, base.pop_to_idx,
+                 base.pos_to_idx, ref_vcf_path=ref_vcf_path, embedding_layer=embedding_layer,
+                 build_ref_data=build_ref_data, n_gpu=n_gpu, name=name, **kw)
+        ds.vcf_genotypes = base.vcf_genotypes
+        return ds
 
     @classmethod
     def from_arrays(cls, vocab, vcf, pos, pop_list, freq, pop_to_idx, pos_to_idx, ref_gt, ref_pos,

@@ -763,6 +763,89 @@ def vcf_format(h1: torch.Tensor, h2: torch.Tensor, gt: torch.Tensor, rows: torch
                                     ptr(bad_count), stream_ptr()), "vcf_format")
 
 
+def _text_ok(text: torch.Tensor, nbytes: int) -> None:
+    assert text.dtype == torch.uint8 and text.dim() == 1 and text.is_contiguous()
+    assert 1 <= nbytes and (nbytes + 15) // 16 * 16 <= text.numel(), "the text buffer must hold the '\\n' padding"
+
+
+def vcf_line_index(text: torch.Tensor, nbytes: int, max_lines: int):
+    """(line_off i64 [max_lines + 1], n_lines i64 [1], both on the device) of the text chunk ``text[:nbytes]``
+    (u8, starts at a line start, padded with '\\n' to a multiple of 16 bytes): the sorted offsets of the
+    lines of non-zero length, then ``nbytes``.  ``n_lines`` may exceed ``max_lines`` (offsets past it
+    are dropped): the caller checks."""
+    N.require_gpu(text)
+    _text_ok(text, nbytes)
+    dev = text.device
+    line_off = torch.empty(max_lines + 1, device=dev, dtype=torch.int64)
+    n_lines = torch.empty(1, device=dev, dtype=torch.int64)
+    nws = N.lib().snvrag_vcf_line_index_ws_bytes(nbytes)
+    ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+    check(N.lib().snvrag_vcf_line_index(ptr(text), nbytes, max_lines, ptr(line_off), ptr(n_lines), ptr(ws), nws,
+                                        stream_ptr()), "vcf_line_index")
+    return line_off, n_lines
+
+
+def vcf_parse_gt(text: torch.Tensor, nbytes: int, line_off: torch.Tensor, n_lines: int, S: int, codes: torch.Tensor,
+                 force_general: bool = False):
+    """Parse lines ``line_off[:n_lines]`` of the chunk: returns (pos i32 [n_lines], flags u32-in-i32
+    [n_lines]) and fills rows [0, n_lines) of ``codes`` u8 [>= n_lines, ld_codes] (one byte per sample;
+    include/snvrag.h lists the flag and code bits).  ``force_general``: every line on the general path."""
+    N.require_gpu(text, line_off, codes)
+    _text_ok(text, nbytes)
+    assert line_off.dtype == torch.int64 and line_off.is_contiguous() and line_off.numel() >= n_lines
+    assert codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous()
+    assert codes.shape[0] >= n_lines and codes.shape[1] >= S and codes.shape[1] % 4 == 0
+    dev = text.device
+    pos = torch.empty(n_lines, device=dev, dtype=torch.int32)
+    flags = torch.empty(n_lines, device=dev, dtype=torch.int32)
+    nws = N.lib().snvrag_vcf_parse_ws_bytes(n_lines, S)
+    ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+    check(N.lib().snvrag_vcf_parse_gt(ptr(text), nbytes, ptr(line_off), n_lines, S, int(bool(force_general)), ptr(pos),
+                                      ptr(flags), ptr(codes), codes.shape[1], ptr(ws), nws, stream_ptr()),
+          "vcf_parse_gt")
+    return pos, flags
+
+
+def vcf_pack_rows(codes: torch.Tensor, n_lines: int, S: int, alt_bits: torch.Tensor, miss_bits: torch.Tensor,
+                  site0: int = 0) -> None:
+    """Rows [0, n_lines) of ``codes`` (records) -> sites [site0, site0 + n_lines) of ``alt_bits`` /
+    ``miss_bits`` u8 [2 S, ld_bits] (haplotype h of sample s = row 2 s + h, site r = bit r & 7 of byte
+    r >> 3).  site0 % 64 == 0, ld_bits % 8 == 0."""
+    N.require_gpu(codes, alt_bits, miss_bits)
+    assert codes.dtype == torch.uint8 and codes.dim() == 2 and codes.is_contiguous() and codes.shape[0] >= n_lines
+    for b in (alt_bits, miss_bits):
+        assert b.dtype == torch.uint8 and b.is_contiguous() and b.shape == (2 * S, alt_bits.shape[1])
+    check(N.lib().snvrag_vcf_pack_rows(ptr(codes), codes.shape[1], n_lines, S, site0, ptr(alt_bits), ptr(miss_bits),
+                                       alt_bits.shape[1], stream_ptr()), "vcf_pack_rows")
+
+
+def panel_gather_bits(bits: torch.Tensor, n_src_sites: int, site_idx: torch.Tensor, n_sites_pad: int,
+                      packed: bool) -> torch.Tensor:
+    """Sites ``site_idx`` (i32 [n]; -1 gives 0) of the bit rows ``bits`` u8 [N, ld_bits] as one window's index
+    rows: u8 [N, n_sites_pad / 8] bits (``packed``) or u8 [N, n_sites_pad] 0/1 codes; padding sites 0."""
+    N.require_gpu(bits, site_idx)
+    assert bits.dtype == torch.uint8 and bits.dim() == 2 and bits.is_contiguous()
+    assert site_idx.dtype == torch.int32 and site_idx.dim() == 1 and site_idx.is_contiguous()
+    out = torch.empty(bits.shape[0], n_sites_pad // 8 if packed else n_sites_pad, device=bits.device,
+                      dtype=torch.uint8)
+    check(N.lib().snvrag_panel_gather_bits(ptr(bits), bits.shape[0], bits.shape[1], n_src_sites, ptr(site_idx),
+                                           site_idx.numel(), n_sites_pad, int(bool(packed)), ptr(out), stream_ptr()),
+          "panel_gather_bits")
+    return out
+
+
+def vcf_unpack_gt(alt_bits: torch.Tensor, miss_bits: torch.Tensor, n_sites: int) -> torch.Tensor:
+    """i8 [n_sites, S, 2] on the device: 0 / 1 from ``alt_bits``, -1 where ``miss_bits`` is set."""
+    N.require_gpu(alt_bits, miss_bits)
+    assert alt_bits.dtype == miss_bits.dtype == torch.uint8 and alt_bits.shape == miss_bits.shape
+    assert alt_bits.dim() == 2 and alt_bits.is_contiguous() and miss_bits.is_contiguous() and alt_bits.shape[0] % 2 == 0
+    S = alt_bits.shape[0] // 2
+    gt = torch.empty(n_sites, S, 2, device=alt_bits.device, dtype=torch.int8)
+    check(N.lib().snvrag_vcf_unpack_gt(ptr(alt_bits), ptr(miss_bits), alt_bits.shape[1], S, n_sites, ptr(gt),
+                                       stream_ptr()), "vcf_unpack_gt")
+    return gt
+
+
 def ln_fwd_train(x: torch.Tensor, r: Optional[torch.Tensor], g: torch.Tensor, b: torch.Tensor, eps: float,
                  p_r: float = 0.0, p_out: float = 0.0, seed: int = 0, slope_x: float = 0.0, slope_r: float = 0.0):
     """(y bf16, s bf16 = act_x(x) + drop(act_r(r)) (x itself when r is None), stats f32 [M, 2]); y

@@ -87,6 +87,20 @@ class PanelIndex:
                    torch.as_tensor(np.asarray(ref_af, np.float32), device=device), ref_offset, n_total)
 
     @classmethod
+    def from_bit_rows(cls, bits: torch.Tensor, site_idx, ref_af, packed: bool = False, ref_offset: int = 0,
+                      n_total: Optional[int] = None, n_src_sites: Optional[int] = None) -> "PanelIndex":
+        """The index of the window whose sites are ``site_idx`` (any order, not contiguous; -1 = a zero
+        site) of the haplotype bit rows ``bits`` u8 [n_ref, ld_bits] on the device (``read_vcf``'s
+        ``alt_bits``, or a contiguous row range of them): ``snvrag_panel_gather_bits``, either layout.
+        Equal to ``from_alleles`` of the same columns."""
+        site_idx = torch.as_tensor(np.ascontiguousarray(site_idx, np.int32)).to(bits.device)
+        n_sites = site_idx.numel()
+        n_src = 8 * bits.shape[1] if n_src_sites is None else int(n_src_sites)
+        data = K.panel_gather_bits(bits.contiguous(), n_src, site_idx, pad_sites(n_sites), packed)
+        return cls(data, n_sites, torch.as_tensor(np.asarray(ref_af, np.float32), device=bits.device), ref_offset,
+                   n_total, packed=packed)
+
+    @classmethod
     def synthetic(cls, n_ref: int, n_sites: int, site_af: torch.Tensor, ref_af: torch.Tensor,
                   seed: int, packed: bool = False) -> "PanelIndex":
         if packed:    # generated straight as bits: the u8 form never exists

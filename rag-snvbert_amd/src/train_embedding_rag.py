@@ -2,8 +2,8 @@
 
 Same command-line surface as the reference (dataset/panel/freq/window/type/pop/pos paths,
 model and optimiser hyper-parameters, rag_k, resume, output) plus:
-  --synthetic N_SAMPLES   build the data in memory (src/dataset/synthetic.py) — this image
-                          has no 1000-Genomes files and no h5py/allel to read them;
+  --synthetic N_SAMPLES   build the data in memory (src/dataset/synthetic.py) instead of reading the
+                          input files (.vcf / .vcf.gz through dataset/vcf_reader.py; H5 needs h5py);
   --max_steps N           stop an epoch after N batches (smoke runs);
   --deterministic         fixed-order reductions in the training step (two runs, one checkpoint);
   --device_features       batches built on the GPU from device-resident tables (same batches).
@@ -100,8 +100,20 @@ def build_data(args, rank: int, world: int):
         for ds in (train, val):
             ds.set_panel_codes(args.panel_codes)
     else:
-        raise SystemExit("reading the reference's H5/VCF inputs needs h5py and scikit-allel, which this image "
-                         "does not have; run with --synthetic N (in-memory data with the same file contract)")
+        # train_embedding_rag.py:122-125, :199-260: vocabulary from the train panel, both datasets from files
+        from .dataset.dataset import PanelData
+        from .dataset.embedding_rag_dataset import EmbeddingRAGDataset
+        from .dataset.vocab import WordVocab
+        missing = [n for n in ("train_dataset", "train_panel", "val_dataset", "val_panel", "refpanel_path",
+                               "freq_path", "window_path", "type_path", "pop_path", "pos_path")
+                   if getattr(args, n) is None]
+        if missing:
+            raise SystemExit("without --synthetic N the input files are needed: missing --" + ", --".join(missing))
+        vocab = WordVocab(list(PanelData.from_file(args.train_panel).pop_class_dict.keys()))
+        mk_ds = lambda data, panel, name: EmbeddingRAGDataset.from_file(
+            vocab, data, panel, args.freq_path, args.window_path, args.type_path, args.pop_path, args.pos_path,
+            ref_vcf_path=args.refpanel_path, name=name, panel_codes=args.panel_codes)
+        train, val = mk_ds(args.train_dataset, args.train_panel, "train"), mk_ds(args.val_dataset, args.val_panel, "val")
     if getattr(args, "device_features", False):
         from .dataset.device_features import DeviceBatchLoader
         mk = lambda ds, sampler, bs: DeviceBatchLoader(ds, sampler, bs, torch.device("cuda", torch.cuda.current_device()))
