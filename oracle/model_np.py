@@ -63,12 +63,16 @@ def softmax(x, axis=-1):
 
 
 # --------------------------------------------------------------------------- #
-def af_embedding(af, sd, p="bert.embedding.af_embedding"):
-    """af_embedding.py:79-91: [sin, cos](2*pi*af*f) -> Linear -> LN -> GELU -> Linear."""
-    fr = sd[p + ".basis_freqs"]
+def af_features(af, fr):
+    """af_embedding.py:79-84: the Fourier feature stage [sin, cos](2*pi*af*f)."""
     ex = (af[..., None].astype(F32) * fr).astype(F32)
     ang = (F32(2 * math.pi) * ex).astype(F32)
-    feat = np.concatenate([np.sin(ang), np.cos(ang)], -1).astype(F32)
+    return np.concatenate([np.sin(ang), np.cos(ang)], -1).astype(F32)
+
+
+def af_embedding(af, sd, p="bert.embedding.af_embedding"):
+    """af_embedding.py:79-91: [sin, cos](2*pi*af*f) -> Linear -> LN -> GELU -> Linear."""
+    feat = af_features(af, sd[p + ".basis_freqs"])
     h = linear(feat, sd, p + ".projection.0")
     h = layernorm(h, sd[p + ".projection.1.weight"], sd[p + ".projection.1.bias"])
     return linear(gelu(h), sd, p + ".projection.3")
@@ -117,14 +121,18 @@ def emb_fusion(emb, pf, af, sd, p="bert.emb_fusion"):
     return layernorm(emb + h, sd[p + ".norm.weight"], sd[p + ".norm.bias"])
 
 
-def rag_fusion(orig, rag, af, af_p, sd, p="bert.rag_fusion"):
-    """fusion.py:131-162 with K=1 (bert.py:197 passes the K-mean as [B,1,L,D])."""
+def af_interaction(af, af_p, sd, q="bert.rag_fusion.af_interaction"):
+    """CrossAFInteraction, fusion.py:82-86: af + res_scale * gate * joint encoding."""
     c = np.stack([af, af_p], -1).astype(F32)
-    q = p + ".af_interaction"
     gate = sigmoid(linear(gelu(linear(c, sd, q + ".gate_net.0")), sd, q + ".gate_net.2"))
     enc = gelu(layernorm(linear(c, sd, q + ".joint_encoder.0"),
                          sd[q + ".joint_encoder.1.weight"], sd[q + ".joint_encoder.1.bias"]))
-    fused_af = (af[..., None] + sd[q + ".res_scale"] * (gate * enc)).astype(F32)
+    return (af[..., None] + sd[q + ".res_scale"] * (gate * enc)).astype(F32)
+
+
+def rag_fusion(orig, rag, af, af_p, sd, p="bert.rag_fusion"):
+    """fusion.py:131-162 with K=1 (bert.py:197 passes the K-mean as [B,1,L,D])."""
+    fused_af = af_interaction(af, af_p, sd, p + ".af_interaction")
     w = sigmoid(linear(gelu(linear(fused_af, sd, p + ".af_adapter.0")), sd, p + ".af_adapter.3"))
     weighted = (rag * w).astype(F32)
     # pooling: softmax over K=1 -> weight exactly 1.0 (fusion.py:145-146)
@@ -161,11 +169,16 @@ def block(x, sd, p, heads):
                      sd[p + ".output_sublayer.norm.weight"], sd[p + ".output_sublayer.norm.bias"])
 
 
-def hap_head(x, af, af_p, sd, p="hap_classifier"):
+def hap_hidden(x, af, af_p, sd, p="hap_classifier"):
+    """foundation_model.py:64-78 up to the input of the last Linear(4D -> 2)."""
     h = np.concatenate([x, af[..., None], af_p[..., None]], -1).astype(F32)
     h = gelu(linear(h, sd, p + ".af_fusion.0"))
     h = layernorm(linear(h, sd, p + ".af_fusion.2"), sd[p + ".af_fusion.3.weight"], sd[p + ".af_fusion.3.bias"])
-    logits = linear(gelu(linear(h, sd, p + ".net.0")), sd, p + ".net.2")
+    return gelu(linear(h, sd, p + ".net.0"))
+
+
+def hap_head(x, af, af_p, sd, p="hap_classifier"):
+    logits = linear(hap_hidden(x, af, af_p, sd, p), sd, p + ".net.2")
     return logits, softmax(logits)
 
 

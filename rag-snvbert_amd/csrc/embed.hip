@@ -143,44 +143,62 @@ __global__ __launch_bounds__(256) void af_gate_kernel(long M, int D, const float
   const int c_lo = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * cpw);
   const int c_hi = min(D, c_lo + cpw);
   // joint_encoder[0] is affine in (af, af_p): enc_n = j0_n a0 + j1_n a1 + jb_n, so its LayerNorm
-  // statistics are mean = mu . (a0, a1, 1) and var = (a0, a1, 1) S (a0, a1, 1)^T with the
-  // centred second moments S of the weight columns — reduced once per workgroup (two passes)
-  // instead of two D-long loops per row
-  __shared__ float red[4][6];
+  // statistics are mean = mu . (a0, a1, 1) and var = |C (a0, a1, 1)^T|^2 / D with the centred
+  // weight columns C = [c0 c1 cb] — reduced once per workgroup instead of two D-long loops per
+  // row.  C = Q R by Gram-Schmidt over the columns themselves, var = |R (a0, a1, 1)^T|^2 / D: a sum
+  // of three squares.  The quadratic form of the second moments C^T C is a signed sum of O(1) terms
+  // and loses the digits of a row whose encoding nearly cancels (variance near the LN epsilon).
+  __shared__ float red[4][3];
   const int wv = threadIdx.x >> 6;
+  auto block_sum3 = [&](float& x, float& y, float& z) {         // over the workgroup, to every thread
+    x = wave_sum(x);
+    y = wave_sum(y);
+    z = wave_sum(z);
+    if ((threadIdx.x & 63) == 0) { red[wv][0] = x; red[wv][1] = y; red[wv][2] = z; }
+    __syncthreads();
+    x = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+    y = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+    z = red[0][2] + red[1][2] + red[2][2] + red[3][2];
+    __syncthreads();
+  };
   float m0 = 0.f, m1 = 0.f, mb = 0.f;
   for (int n = threadIdx.x; n < D; n += 256) {
     m0 += w.j_w[n * 2];
     m1 += w.j_w[n * 2 + 1];
     mb += w.j_b[n];
   }
-  m0 = wave_sum(m0);
-  m1 = wave_sum(m1);
-  mb = wave_sum(mb);
-  if ((threadIdx.x & 63) == 0) { red[wv][0] = m0; red[wv][1] = m1; red[wv][2] = mb; }
-  __syncthreads();
-  m0 = (red[0][0] + red[1][0] + red[2][0] + red[3][0]) / D;
-  m1 = (red[0][1] + red[1][1] + red[2][1] + red[3][1]) / D;
-  mb = (red[0][2] + red[1][2] + red[2][2] + red[3][2]) / D;
-  __syncthreads();
-  float sm[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};                // S00 S11 S01 S0b S1b Sbb
+  block_sum3(m0, m1, mb);
+  m0 /= D;
+  m1 /= D;
+  mb /= D;
+  float s00 = 0.f, s01 = 0.f, s0b = 0.f;                        // q0 = c0 / |c0|
   for (int n = threadIdx.x; n < D; n += 256) {
     const float c0 = w.j_w[n * 2] - m0, c1 = w.j_w[n * 2 + 1] - m1, cb = w.j_b[n] - mb;
-    sm[0] += c0 * c0;
-    sm[1] += c1 * c1;
-    sm[2] += c0 * c1;
-    sm[3] += c0 * cb;
-    sm[4] += c1 * cb;
-    sm[5] += cb * cb;
+    s00 += c0 * c0;
+    s01 += c0 * c1;
+    s0b += c0 * cb;
   }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    sm[i] = wave_sum(sm[i]);
-    if ((threadIdx.x & 63) == 0) red[wv][i] = sm[i];
+  block_sum3(s00, s01, s0b);
+  const float i00 = s00 > 0.f ? 1.0f / sqrtf(s00) : 0.f;
+  const float r00 = s00 * i00, r01 = s01 * i00, r0b = s0b * i00;
+  float s11 = 0.f, s1b = 0.f, nil = 0.f;                        // q1 = (c1 - r01 q0) / |.|
+  for (int n = threadIdx.x; n < D; n += 256) {
+    const float q0 = (w.j_w[n * 2] - m0) * i00;
+    const float c1 = (w.j_w[n * 2 + 1] - m1) - r01 * q0, cb = (w.j_b[n] - mb) - r0b * q0;
+    s11 += c1 * c1;
+    s1b += c1 * cb;
   }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 6; ++i) sm[i] = (red[0][i] + red[1][i] + red[2][i] + red[3][i]) / D;
+  block_sum3(s11, s1b, nil);
+  const float i11 = s11 > 0.f ? 1.0f / sqrtf(s11) : 0.f;
+  const float r11 = s11 * i11, r1b = s1b * i11;
+  float sbb = 0.f;                                              // |cb - r0b q0 - r1b q1|^2
+  for (int n = threadIdx.x; n < D; n += 256) {
+    const float q0 = (w.j_w[n * 2] - m0) * i00;
+    const float q1 = ((w.j_w[n * 2 + 1] - m1) - r01 * q0) * i11;
+    const float cb = ((w.j_b[n] - mb) - r0b * q0) - r1b * q1;
+    sbb += cb * cb;
+  }
+  block_sum3(sbb, nil, nil);
   float a0[AF_R], a1[AF_R], mean[AF_R], rstd[AF_R], hid[AF_R][32];
 #pragma unroll
   for (int r = 0; r < AF_R; ++r) {
@@ -189,9 +207,9 @@ __global__ __launch_bounds__(256) void af_gate_kernel(long M, int D, const float
     a0[r] = ok ? af[m] : 0.f;
     a1[r] = ok ? afp[m] : 0.f;
     mean[r] = m0 * a0[r] + m1 * a1[r] + mb;
-    const float var = a0[r] * a0[r] * sm[0] + a1[r] * a1[r] * sm[1] +
-                      2.f * (a0[r] * a1[r] * sm[2] + a0[r] * sm[3] + a1[r] * sm[4]) + sm[5];
-    rstd[r] = 1.0f / sqrtf(fmaxf(var, 0.f) + 1e-5f);
+    const float y0 = r00 * a0[r] + r01 * a1[r] + r0b, y1 = r11 * a1[r] + r1b;
+    const float var = (y0 * y0 + y1 * y1 + sbb) / D;
+    rstd[r] = 1.0f / sqrtf(var + 1e-5f);
 #pragma unroll
     for (int u = 0; u < 32; ++u)
       hid[r][u] = gelu_erf(w.g1_w[u * 2] * a0[r] + w.g1_w[u * 2 + 1] * a1[r] + w.g1_b[u]);

@@ -225,15 +225,28 @@ def af_features(af: torch.Tensor, freqs: torch.Tensor, dtype: torch.dtype) -> to
 
 def embed_tokens(tok: torch.Tensor, W: torch.Tensor, pe: torch.Tensor, afemb: Optional[torch.Tensor],
                  af_period: int, dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    N.require_gpu(tok)
+    """out [nseq, L, D] = W[clamp(tok)] + pe[:L] + afemb[(s % af_period if af_period > 0 else s)];
+    ``afemb`` [rows, L, D] (or [L, D] for one shared row), f32 or bf16; ``out`` (e.g. the leading
+    rows of a larger block) is filled in place.  Only pointers cross the boundary, so every
+    tensor must be the contiguous layout the kernel indexes: anything else raises."""
+    N.require_gpu(tok, W, pe, afemb, out)
     assert tok.dtype == torch.int64
     nseq, L = tok.shape
     D = W.shape[1]
+    if W.dtype != torch.float32 or pe.dtype != torch.float32 or pe.dim() != 2 or pe.shape[0] < L or pe.shape[1] != D:
+        raise ValueError(f"W and pe must be float32 with pe [>= {L}, {D}], got pe {tuple(pe.shape)} {pe.dtype}, W {W.dtype}")
+    if afemb is not None:
+        rows = af_period if af_period > 0 else nseq
+        if afemb.shape[-2:] != (L, D) or afemb.numel() != rows * L * D:
+            raise ValueError(f"afemb must be [{rows}, {L}, {D}], got {tuple(afemb.shape)}")
+        _c(afemb)
     if out is None:
         out = torch.empty(nseq, L, D, device=tok.device, dtype=dtype)
+    elif out.dtype != dtype or tuple(out.shape) != (nseq, L, D):
+        raise ValueError(f"out must be {dtype} [{nseq}, {L}, {D}], got {out.dtype} {tuple(out.shape)}")
     check(N.lib().snvrag_embed_tokens(_dt(dtype), nseq, L, D, ptr(_c(tok)), ptr(_c(W)), W.shape[0],
                                       ptr(_c(pe)), ptr(afemb), _dt(afemb.dtype) if afemb is not None else 0,
-                                      af_period, ptr(out), stream_ptr()), "embed_tokens")
+                                      af_period, ptr(_c(out)), stream_ptr()), "embed_tokens")
     return out
 
 
