@@ -792,6 +792,31 @@ int snvrag_panel_gather_bits(const uint8_t* bits, int64_t N, int64_t ld_bits, in
 int snvrag_vcf_unpack_gt(const uint8_t* alt_bits, const uint8_t* miss_bits, int64_t ld_bits, int64_t S,
                          int64_t n_sites, int8_t* gt, void* stream);
 
+/* Device inflate of BGZF blocks (csrc/inflate.hip; the gzip layer under allel.read_vcf for a bgzipped
+ * .vcf.gz).  The decoder is csrc/inflate_core.h; its specification, status for status, is
+ * src/dataset/bgzf.py inflate_block_host.
+ *
+ * snvrag_bgzf_inflate: block b of the table is the raw deflate stream comp[in_off, in_off + in_len) and is
+ *   inflated to text[out_off, out_off + isize); status i32 [n_blocks] is written for every block.
+ *   table: i64 [n_blocks][4] = { in_off, out_off, in_len | isize << 32 (two i32 halves), crc (u32 in the low
+ *   half) }, 32 bytes per block.  table_host is read and checked here, then copied into table_dev (device,
+ *   32 n_blocks bytes, 8-byte aligned) on the stream: with a pinned table_host the caller keeps it unchanged
+ *   until the stream has passed the copy.  out_off may be any byte offset.  A block is written only when it
+ *   inflated (status 0 or 9), and then whole; no byte outside its range is touched.
+ *   Refused with no launch: in_len < 0, isize outside [0, 65536], a range outside comp_bytes / text_bytes.
+ *   Status (SNVRAG_INFL_*): the first condition met in stream order.  Input past in_len reads as zero bits
+ *   and gives 6 once the bit position passes 8 in_len; 7 / 8 compare with isize alone, which is also the
+ *   output bound; 9 = the CRC-32 of the inflated bytes (folded into the same kernel: per-lane segments
+ *   combined with x^(8n) mod P) differs from the table's.
+ * snvrag_text_last_newline: *out (device i64) = the index of the last '\n' of text[0, nbytes), or -1.
+ *   text 16-byte aligned.  A max-reduction in one workgroup: no float, no atomics. */
+enum { SNVRAG_INFL_OK = 0, SNVRAG_INFL_BAD_TYPE = 1, SNVRAG_INFL_BAD_STORED = 2, SNVRAG_INFL_BAD_LENGTHS = 3,
+       SNVRAG_INFL_BAD_SYMBOL = 4, SNVRAG_INFL_BAD_DISTANCE = 5, SNVRAG_INFL_INPUT_END = 6,
+       SNVRAG_INFL_OUTPUT_FULL = 7, SNVRAG_INFL_OUTPUT_SHORT = 8, SNVRAG_INFL_BAD_CRC = 9 };
+int snvrag_bgzf_inflate(const uint8_t* comp, int64_t comp_bytes, const int64_t* table_host, int64_t* table_dev,
+                        int64_t n_blocks, uint8_t* text, int64_t text_bytes, int32_t* status, void* stream);
+int snvrag_text_last_newline(const uint8_t* text, int64_t nbytes, int64_t* out, void* stream);
+
 /* self tests of MFMA operand/accumulator layouts used by the kernels (GPU only):
  * returns 0 when the i8 / bf16 / f32 MFMA maps match the CPU product. */
 int snvrag_selftest_mfma(void* stream);

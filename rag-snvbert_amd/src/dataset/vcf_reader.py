@@ -28,8 +28,16 @@ into the next; two pinned host buffers alternate, chunk c + 1 is read (and infla
 stream while chunk c parses.  Records beyond the last multiple of 64 stay in the code buffer for the next
 chunk, so every chunk's bit block is whole bytes; the blocks are concatenated at the end.
 
-Not covered: inflate on the device, a rank reading only its shard's sample columns, multi-allelic
-splitting (any allele number > 0 is ALT), REF / ALT / ID strings, h5 files.
+``inflate="device"`` (``--vcf_inflate device``; ``DEFAULT_INFLATE`` / ``set_default_inflate``) inflates a BGZF
+``.vcf.gz`` on the GPU (csrc/inflate.hip, one wave per block; ``bgzf.py`` walks the block headers and is the
+kernel's specification): raw file bytes go up, the blocks of a chunk are inflated behind the previous chunk's
+tail straight into the text buffer, the chunk is cut at its last newline by a device reduction, and the line
+index, parse and pack steps run unchanged.  Only the few blocks that hold the header are inflated on the host.
+A file that is not BGZF (plain text, a single-member gzip) takes the host path with one line of notice.
+
+Not covered: single-member gzip on the device, ``.csi`` / ``.tbi`` random access, BGZF output from the VCF
+writer, a rank reading only its shard's sample columns, multi-allelic splitting (any allele number > 0 is
+ALT), REF / ALT / ID strings, h5 files.
 """
 
 from __future__ import annotations
@@ -52,6 +60,18 @@ FLAG_TEXT = {FLAG_FORMAT: "FORMAT does not begin with GT",
 CODE_ALT1, CODE_ALT2, CODE_MISS1, CODE_MISS2, CODE_SLASH = 1, 2, 4, 8, 16
 DEFAULT_CHUNK_BYTES = 256 << 20
 MAX_CHUNK_BYTES = (1 << 31) - 64
+INFLATE_MODES = ("host", "device")
+DEFAULT_INFLATE = "host"               # what read_vcf(inflate=None) does; set_default_inflate changes it
+MAX_CHUNK_BLOCKS = 1 << 16             # BGZF blocks per chunk of the device inflate (empty blocks are legal)
+RAW_PIECE = 1 << 20                    # raw file bytes per read of the device inflate
+
+
+def set_default_inflate(mode: str) -> None:
+    """Where ``read_vcf`` inflates BGZF files unless told otherwise: "host" (zlib) or "device"."""
+    global DEFAULT_INFLATE
+    if mode not in INFLATE_MODES:
+        raise ValueError(f"inflate must be one of {INFLATE_MODES}, not {mode!r}")
+    DEFAULT_INFLATE = mode
 
 
 def is_vcf_path(path) -> bool:
@@ -217,18 +237,101 @@ def _record_line(path, record: int) -> int:
     raise ValueError(f"{path}: record {record} not found")
 
 
-def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general: bool = False) -> VcfGenotypes:
-    """POS and GT of the VCF at ``path`` (``.gz`` / BGZF inflated on the host, streaming), the body
-    parsed on ``device``.  ``force_general`` sends every line through the general parse path (same
-    result).  ``ValueError``: what ``parse_vcf_host`` raises for the file, or a line longer than
-    ``chunk_bytes``."""
+class _ChunkParser:
+    """What follows a chunk's text on the device, for either source of the text: line index, parse, and the
+    pack of every whole group of 64 records; ``finish`` joins the parts."""
+
+    def __init__(self, path, name, dev, samples, chunk_bytes, force_general):
+        import torch
+        self.path, self.name, self.dev, self.samples, self.force_general = path, name, dev, samples, force_general
+        self.S = S = len(samples)
+        # a record holds at least 8 one-byte columns, GT and S one-byte cells, each with its separator
+        self.max_lines = chunk_bytes // (2 * S + 17) + 1
+        self.codes = torch.empty(self.max_lines + 64, (S + 3) // 4 * 4, device=dev, dtype=torch.uint8)
+        self.pos_parts, self.flag_parts, self.alt_parts, self.miss_parts = [], [], [], []
+        self.carry = self.n_records = 0
+
+    def _pack(self, n):
+        import torch
+        from .. import kernels as K
+        ld = ((n + 7) // 8 + 7) // 8 * 8
+        alt = torch.empty(2 * self.S, ld, device=self.dev, dtype=torch.uint8)
+        miss = torch.empty(2 * self.S, ld, device=self.dev, dtype=torch.uint8)
+        K.vcf_pack_rows(self.codes, n, self.S, alt, miss)
+        self.alt_parts.append(alt[:, :(n + 7) // 8])
+        self.miss_parts.append(miss[:, :(n + 7) // 8])
+
+    def chunk(self, text, cut, last, parsed_event, stream):
+        """``text[:cut]`` (padded with '\\n' to 16 bytes) is a chunk of whole lines; ``last``: nothing follows."""
+        from .. import kernels as K
+        line_off, n_lines = K.vcf_line_index(text, cut, self.max_lines)
+        nl = int(n_lines.item())                       # also: the chunk's upload has left the host
+        if nl > self.max_lines:                        # a line shorter than any record
+            parse_vcf_host(self.path)
+            raise ValueError(f"{self.name}: a body line is shorter than a record of {self.S} samples")
+        if nl:
+            p, f = K.vcf_parse_gt(text, cut, line_off, nl, self.S, self.codes[self.carry:], self.force_general)
+            self.pos_parts.append(p)
+            self.flag_parts.append(f)
+        parsed_event.record(stream)
+        total = self.carry + nl
+        full = total if last else total // 64 * 64
+        if full:
+            self._pack(full)
+            self.carry = total - full
+            if self.carry:                             # fewer than 64 <= full rows: no overlap
+                self.codes[:self.carry].copy_(self.codes[full:total])
+        else:
+            self.carry = total
+        self.n_records += nl
+
+    def finish(self) -> "VcfGenotypes":
+        import torch
+        dev, S, name = self.dev, self.S, self.name
+        if self.carry:                                 # the file ended in an empty chunk
+            self._pack(self.carry)
+        if self.n_records:
+            flags = torch.cat(self.flag_parts).cpu().numpy().view(np.uint32)
+            pos = torch.cat(self.pos_parts).cpu().numpy()
+            alt_bits = torch.cat(self.alt_parts, 1).contiguous()
+            miss_bits = torch.cat(self.miss_parts, 1).contiguous()
+        else:
+            flags, pos = np.zeros(0, np.uint32), np.zeros(0, np.int32)
+            alt_bits = torch.zeros(2 * S, 0, device=dev, dtype=torch.uint8)
+            miss_bits = torch.zeros(2 * S, 0, device=dev, dtype=torch.uint8)
+        torch.cuda.synchronize(dev)
+        bad = np.flatnonzero(flags & np.uint32(FLAG_ERRORS | FLAG_OFFSET))
+        if bad.size:
+            r = int(bad[0])
+            if int(flags[r]) & FLAG_OFFSET:
+                raise RuntimeError(f"{name}: record {r}: the line index gave an offset outside its chunk")
+            raise flag_error(name, _record_line(self.path, r), int(flags[r]) & FLAG_ERRORS)
+        seen = int(np.bitwise_or.reduce(flags >> np.uint32(8))) if flags.size else 0
+        return VcfGenotypes(self.samples, pos.astype(np.int32, copy=False), alt_bits, miss_bits, self.n_records,
+                            bool(seen & (CODE_MISS1 | CODE_MISS2)), not seen & CODE_SLASH)
+
+
+def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general: bool = False,
+             inflate: str = None) -> VcfGenotypes:
+    """POS and GT of the VCF at ``path``, the body parsed on ``device``.  ``.gz`` / BGZF is inflated on the host
+    (streaming), or with ``inflate="device"`` (``None``: ``DEFAULT_INFLATE``) on the GPU when the file is BGZF.
+    ``force_general`` sends every line through the general parse path (same result).  ``ValueError``: what
+    ``parse_vcf_host`` raises for the file, a line longer than ``chunk_bytes``, or a BGZF block that does not
+    inflate (``inflate="device"``: "<path>: BGZF block at byte <file offset>: <what>")."""
     import torch
-    from .. import kernels as K
     from .. import native as N
     N.require_gpu()
     if not 64 <= chunk_bytes <= MAX_CHUNK_BYTES:
         raise ValueError(f"chunk_bytes must be in [64, {MAX_CHUNK_BYTES}]")
+    mode = DEFAULT_INFLATE if inflate is None else inflate
+    if mode not in INFLATE_MODES:
+        raise ValueError(f"inflate must be one of {INFLATE_MODES}, not {mode!r}")
     name, dev = str(path), torch.device(device)
+    if mode == "device":
+        from .bgzf import is_bgzf
+        if is_bgzf(path):
+            return _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general)
+        print(f"{name}: not a BGZF file, inflate=\"device\" does not apply: reading it on the host")
     with _open(path) as fh:
         if not isinstance(fh, gzip.GzipFile):               # no buffer larger than the file itself
             chunk_bytes = min(chunk_bytes, max(64, os.path.getsize(path) + 1))
@@ -242,21 +345,15 @@ def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general
                 raise ValueError(f"{name}: a record in front of the #CHROM header")
         if samples is None:
             raise ValueError(f"{name}: no #CHROM header")
-        S = len(samples)
-        ld_codes = (S + 3) // 4 * 4
-        # a record holds at least 8 one-byte columns, GT and S one-byte cells, each with its separator
-        max_lines = chunk_bytes // (2 * S + 17) + 1
         cap = (chunk_bytes + 15) // 16 * 16
-        pos_parts, flag_parts, alt_parts, miss_parts = [], [], [], []
-        n_records = 0
         with torch.cuda.device(dev):
             main, side = torch.cuda.current_stream(), torch.cuda.Stream()
             pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
             text = [torch.empty(cap, device=dev, dtype=torch.uint8) for _ in range(2)]
             uploaded = [torch.cuda.Event(), torch.cuda.Event()]
             parsed = [torch.cuda.Event(), torch.cuda.Event()]
-            codes = torch.empty(max_lines + 64, ld_codes, device=dev, dtype=torch.uint8)
-            carry, tail, eof, c = 0, b"", False, 0
+            parser = _ChunkParser(path, name, dev, samples, chunk_bytes, force_general)
+            tail, eof, c = b"", False, 0
             while not eof or tail:
                 b = c & 1
                 buf = pinned[b].numpy()                      # chunk c - 2 left it: its parse was waited for below
@@ -286,68 +383,193 @@ def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general
                     text[b][:padded].copy_(pinned[b][:padded], non_blocking=True)
                     uploaded[b].record(side)
                 main.wait_event(uploaded[b])
-                line_off, n_lines = K.vcf_line_index(text[b], cut, max_lines)
-                nl = int(n_lines.item())                       # also: pinned[b] has left the host
-                if nl > max_lines:                             # a line shorter than any record
-                    parse_vcf_host(path)
-                    raise ValueError(f"{name}: a body line is shorter than a record of {S} samples")
-                if nl:
-                    p, f = K.vcf_parse_gt(text[b], cut, line_off, nl, S, codes[carry:], force_general)
-                    pos_parts.append(p)
-                    flag_parts.append(f)
-                parsed[b].record(main)
-                total = carry + nl
-                full = total if eof and not tail else total // 64 * 64
-                if full:
-                    ld = ((full + 7) // 8 + 7) // 8 * 8
-                    alt = torch.empty(2 * S, ld, device=dev, dtype=torch.uint8)
-                    miss = torch.empty(2 * S, ld, device=dev, dtype=torch.uint8)
-                    K.vcf_pack_rows(codes, full, S, alt, miss)
-                    alt_parts.append(alt[:, :(full + 7) // 8])
-                    miss_parts.append(miss[:, :(full + 7) // 8])
-                    carry = total - full
-                    if carry:                                  # fewer than 64 <= full rows: no overlap
-                        codes[:carry].copy_(codes[full:total])
-                else:
-                    carry = total
-                n_records += nl
-            if carry:                                          # the file ended in an empty chunk
-                ld = ((carry + 7) // 8 + 7) // 8 * 8
-                alt = torch.empty(2 * S, ld, device=dev, dtype=torch.uint8)
-                miss = torch.empty(2 * S, ld, device=dev, dtype=torch.uint8)
-                K.vcf_pack_rows(codes, carry, S, alt, miss)
-                alt_parts.append(alt[:, :(carry + 7) // 8])
-                miss_parts.append(miss[:, :(carry + 7) // 8])
+                parser.chunk(text[b], cut, eof and not tail, parsed[b], main)
             main.wait_stream(side)
-            if n_records:
-                flags = torch.cat(flag_parts).cpu().numpy().view(np.uint32)
-                pos = torch.cat(pos_parts).cpu().numpy()
-                alt_bits = torch.cat(alt_parts, 1).contiguous()
-                miss_bits = torch.cat(miss_parts, 1).contiguous()
-            else:
-                flags, pos = np.zeros(0, np.uint32), np.zeros(0, np.int32)
-                alt_bits = torch.zeros(2 * S, 0, device=dev, dtype=torch.uint8)
-                miss_bits = torch.zeros(2 * S, 0, device=dev, dtype=torch.uint8)
-            torch.cuda.synchronize(dev)
-    bad = np.flatnonzero(flags & np.uint32(FLAG_ERRORS | FLAG_OFFSET))
-    if bad.size:
-        r = int(bad[0])
-        if int(flags[r]) & FLAG_OFFSET:
-            raise RuntimeError(f"{name}: record {r}: the line index gave an offset outside its chunk")
-        raise flag_error(name, _record_line(path, r), int(flags[r]) & FLAG_ERRORS)
-    seen = int(np.bitwise_or.reduce(flags >> np.uint32(8))) if flags.size else 0
-    return VcfGenotypes(samples, pos.astype(np.int32, copy=False), alt_bits, miss_bits, n_records,
-                        bool(seen & (CODE_MISS1 | CODE_MISS2)), not seen & CODE_SLASH)
+            return parser.finish()
 
 
-def write_gt_vcf(path, samples, pos, gt, chrom: str = "1", fmt: str = "GT", extra=None, phased=True) -> None:
+def _bgzf_error(name: str, file_off: int, what: str) -> ValueError:
+    return ValueError(f"{name}: BGZF block at byte {file_off}: {what}")
+
+
+def _bgzf_header(path, name, fh):
+    """Inflate blocks from the front on the host until the #CHROM line is whole.  Returns (samples, the file
+    offset of the block that holds the first body byte, the header bytes in front of it in that block)."""
+    import zlib
+    from . import bgzf
+    head, starts, buf, pos, scan, ended = bytearray(), [], b"", 0, 0, False
+    while True:
+        piece = fh.read(RAW_PIECE)
+        buf += piece
+        try:
+            blocks, used = bgzf.bgzf_blocks(buf, pos)
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+        if not piece:
+            if used < len(buf):
+                raise _bgzf_error(name, pos + used, "truncated")
+            ended = True
+        for blk in blocks:
+            o = blk.payload_off
+            payload = bytes(buf[o:o + blk.payload_len])
+            try:
+                data = zlib.decompress(payload, -15)
+                ok = len(data) == blk.isize and zlib.crc32(data) == blk.crc
+            except zlib.error:
+                ok = False
+            if not ok:
+                st = bgzf.inflate_member_host(payload, blk.isize, blk.crc)[1]
+                raise _bgzf_error(name, blk.file_off, bgzf.STATUS_TEXT.get(st, "does not inflate"))
+            starts.append((blk.file_off, len(head), o + blk.payload_len + 8 - (blk.file_off - pos)))
+            head += data
+            while True:                                        # whole lines of the header so far
+                e = head.find(b"\n", scan)
+                if e < 0:
+                    break
+                line = bytes(head[scan:e])
+                if line.startswith(b"#CHROM"):
+                    body0 = e + 1
+                    for file_off, start, size in reversed(starts):
+                        if start <= body0:
+                            if body0 == len(head):             # the body begins with the next block
+                                return _header_samples(line, name), file_off + size, 0
+                            return _header_samples(line, name), file_off, body0 - start
+                if line.strip() and not line.startswith(b"#"):
+                    parse_vcf_host(path)                       # raises the specification's error
+                    raise ValueError(f"{name}: a record in front of the #CHROM header")
+                scan = e + 1
+        buf, pos = buf[used:], pos + used
+        if ended:
+            line = bytes(head[scan:])
+            if line.startswith(b"#CHROM"):                     # a header line without its newline ends the file
+                return _header_samples(line, name), pos, 0
+            if line.strip() and not line.startswith(b"#"):
+                parse_vcf_host(path)
+            raise ValueError(f"{name}: no #CHROM header")
+
+
+def _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general) -> VcfGenotypes:
+    """``read_vcf`` of a BGZF file with the blocks inflated on the device.  Per chunk: raw bytes are read into
+    one of two pinned buffers RAW_PIECE at a time and their block headers walked until the next block would not
+    fit (``tail + sum ISIZE <= chunk_bytes``, at most MAX_CHUNK_BLOCKS blocks, the raw buffer); the taken bytes
+    go up on the side stream; the blocks are inflated into ``text[b]`` behind the previous chunk's tail; status
+    and the index of the last newline come back in one read; the tail is copied to the other text buffer, the
+    chunk padded and parsed."""
+    import torch
+    from .. import kernels as K
+    from . import bgzf
+    with open(path, "rb") as fh:
+        samples, off0, skip = _bgzf_header(path, name, fh)
+        fh.seek(off0)
+        cap = (chunk_bytes + 15) // 16 * 16
+        rawcap = min(chunk_bytes // 4 + 2 * RAW_PIECE, max(os.path.getsize(path) - off0, 0) + 64)
+        with torch.cuda.device(dev):
+            main, side = torch.cuda.current_stream(), torch.cuda.Stream()
+            raw = [torch.empty(rawcap, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            tables = [torch.empty(MAX_CHUNK_BLOCKS, 4, dtype=torch.int64).pin_memory() for _ in range(2)]
+            comp = [torch.empty(rawcap, device=dev, dtype=torch.uint8) for _ in range(2)]
+            table_dev = torch.empty(MAX_CHUNK_BLOCKS, 4, device=dev, dtype=torch.int64)
+            text = [torch.empty(cap, device=dev, dtype=torch.uint8) for _ in range(2)]
+            res = torch.empty(2 + MAX_CHUNK_BLOCKS, device=dev, dtype=torch.int32)     # last newline (i64), status
+            uploaded = [torch.cuda.Event(), torch.cuda.Event()]
+            parsed = [torch.cuda.Event(), torch.cuda.Event()]
+            parser = _ChunkParser(path, name, dev, samples, chunk_bytes, force_general)
+            rest = np.zeros(0, np.uint8)           # raw bytes read and not yet taken: whole blocks and a partial one
+            base = off0                            # file offset of rest[0]
+            tail_len, eof, c = 0, False, 0
+            deferred = None                        # a record-level error: raised once every block has inflated
+            while not eof or tail_len or rest.size:
+                b = c & 1
+                # raw[b] and tables[b] were last read by chunk c - 2's copies, which chunk c - 1's read-back followed
+                buf = raw[b].numpy()
+                n = rest.size
+                buf[:n] = rest
+                view, o, taken, out_bytes, full = memoryview(buf), 0, [], tail_len, False
+                while not full:
+                    try:
+                        blocks, used = bgzf.bgzf_blocks(view[o:n], base + o)
+                    except ValueError as e:
+                        raise ValueError(f"{name}: {e}") from None
+                    used_fit = 0
+                    for blk in blocks:
+                        if out_bytes + blk.isize > chunk_bytes or len(taken) == MAX_CHUNK_BLOCKS:
+                            full = True
+                            break
+                        taken.append((blk.file_off, o + blk.payload_off, blk.payload_len, out_bytes, blk.isize, blk.crc))
+                        out_bytes += blk.isize
+                        used_fit = blk.payload_off + blk.payload_len + 8
+                    o += used_fit
+                    if full or eof:
+                        break
+                    if n == rawcap:
+                        if not taken and not blocks:
+                            raise _bgzf_error(name, base, "larger than 64 KiB")      # cannot happen: rawcap > 64 KiB
+                        break
+                    got = fh.readinto(view[n:min(rawcap, n + RAW_PIECE)])
+                    if not got:
+                        eof = True
+                    n += got or 0
+                if eof and not full and o < n:
+                    raise _bgzf_error(name, base + o, "truncated")
+                if not taken and o < n:
+                    raise ValueError(f"{name}: chunk_bytes = {chunk_bytes} is too small for the BGZF block at byte "
+                                     f"{base + o} behind a line tail of {tail_len} bytes (a line longer than chunk_bytes?)")
+                rest, base = buf[o:n].copy(), base + o
+                last = eof and not rest.size
+                c += 1
+                nb, n_text = len(taken), out_bytes
+                if n_text == 0:
+                    continue
+                if nb:
+                    cols = list(zip(*taken))
+                    table = K.bgzf_table(cols[1], cols[3], cols[2], cols[4], cols[5], tables[b])
+                    with torch.cuda.stream(side):              # comp[b] was last read by chunk c - 2's inflate: main has passed it
+                        side.wait_stream(main)
+                        comp[b][:o].copy_(raw[b][:o], non_blocking=True)
+                        uploaded[b].record(side)
+                    main.wait_event(uploaded[b])
+                    K.bgzf_inflate(comp[b][:o], table, text[b], res[2:], table_dev)
+                    if skip:                                   # the header lines in front of the body in its first block
+                        text[b][:skip].fill_(10)
+                        skip = 0
+                if last and n_text < chunk_bytes:
+                    text[b][n_text:n_text + 1].fill_(10)       # a last line without its newline
+                    n_text += 1
+                K.text_last_newline(text[b], n_text, res[:2].view(torch.int64))
+                host = res[:2 + nb].cpu().numpy()
+                for i in np.flatnonzero(host[2:]):
+                    raise _bgzf_error(name, taken[int(i)][0], bgzf.STATUS_TEXT.get(int(host[2 + i]), "does not inflate"))
+                cut = int(host[:2].view(np.int64)[0]) + 1
+                if cut == 0:
+                    raise ValueError(f"{name}: a line is longer than chunk_bytes = {chunk_bytes}")
+                tail_len = n_text - cut
+                if tail_len:                                   # text[b ^ 1] was last read by chunk c - 1's parse, on this stream
+                    text[b ^ 1][:tail_len].copy_(text[b][cut:n_text])
+                padded = (cut + 15) // 16 * 16
+                text[b][cut:padded].fill_(10)
+                if deferred is None:
+                    try:
+                        parser.chunk(text[b], cut, last and not tail_len, parsed[b], main)
+                    except (ValueError, OSError, EOFError) as e:   # a BGZF error of a later block comes first (the
+                        deferred = e                               # host parser, asked for its error, may meet that block)
+            main.wait_stream(side)
+            if deferred is not None:
+                raise deferred
+            return parser.finish()
+
+
+def write_gt_vcf(path, samples, pos, gt, chrom: str = "1", fmt: str = "GT", extra=None, phased=True,
+                 bgzf: bool = False) -> None:
     """A minimal VCF of ``gt`` [n, S, 2] (allele numbers, -1 = '.'): what the tools and tests read back.
     ``fmt`` "GT" writes ``a|b`` cells; a longer FORMAT appends ``extra`` (a string per cell, or one string
-    for all) behind the call.  ``.gz`` paths are gzip-compressed."""
+    for all) behind the call.  ``.gz`` paths are gzip-compressed: one plain member, or BGZF blocks with ``bgzf``."""
     gt = np.asarray(gt)
     sep = "|" if phased else "/"
     sym = np.array(["."] + [str(i) for i in range(128)])
     opener = gzip.open if str(path).endswith(".gz") else open
+    if bgzf:
+        from .bgzf import BgzfWriter
+        opener = lambda p, mode: BgzfWriter(p)
     with opener(path, "wb") as fh:
         fh.write(b"##fileformat=VCFv4.2\n")
         fh.write(("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join(samples) + "\n").encode())

@@ -74,6 +74,9 @@ def parse_args(argv=None):
     p.add_argument("--dist_backend", default="nccl", choices=["nccl", "gloo"],
                    help="WORLD_SIZE > 1 (torch.distributed.run, one process per GPU): nccl (= RCCL) or gloo "
                         "(host-staged: the multi-rank tests with every rank on one GPU)")
+    p.add_argument("--vcf_inflate", default="host", choices=["host", "device"],
+                   help="where BGZF .vcf.gz inputs are inflated: host (zlib) or device (csrc/inflate.hip, one wave "
+                        "per block); the same arrays either way, files that are not BGZF stay on the host")
     return p.parse_args(argv)
 
 
@@ -282,6 +285,8 @@ def _empty_rows(key, dev, k):
 
 def infer(argv=None):
     args = parse_args(argv)
+    from .dataset.vcf_reader import set_default_inflate
+    set_default_inflate(args.vcf_inflate)
     if not torch.cuda.is_available():
         raise SystemExit("imputation runs on the MI355X kernels only (no CPU fallback)")
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -859,6 +859,57 @@ def vcf_unpack_gt(alt_bits: torch.Tensor, miss_bits: torch.Tensor, n_sites: int)
     return gt
 
 
+def bgzf_table(in_off, out_off, in_len, isize, crc, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The block table of ``bgzf_inflate`` from five sequences: host i64 [n, 4] = in_off, out_off,
+    in_len | isize << 32, crc (into the first rows of ``out`` when given, e.g. a pinned buffer)."""
+    import numpy as np
+    n = len(in_off)
+    t = np.empty((n, 4), np.int64)
+    t[:, 0], t[:, 1] = in_off, out_off
+    t[:, 2] = np.asarray(in_len, np.int64) & 0xffffffff | np.asarray(isize, np.int64) << 32
+    t[:, 3] = np.asarray(crc, np.int64) & 0xffffffff
+    if out is None:
+        return torch.from_numpy(t)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.shape[0] >= n and out.shape[1:] == (4,)
+    out.numpy()[:n] = t
+    return out[:n]
+
+
+def bgzf_inflate(comp: torch.Tensor, table: torch.Tensor, text: torch.Tensor, status: Optional[torch.Tensor] = None,
+                 table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Inflate the BGZF blocks of ``table`` (host i64 [n, 4], ``bgzf_table``) from ``comp`` (device u8) into
+    ``text`` (device u8) at their ``out_off``; returns status i32 [n] on the device (src/dataset/bgzf.py lists the
+    codes; a block is written only with status 0 or 9).  A pinned ``table`` must stay unchanged until the
+    stream has passed this call."""
+    N.require_gpu(comp, text)
+    assert comp.dtype == torch.uint8 and comp.dim() == 1 and comp.is_contiguous()
+    assert text.dtype == torch.uint8 and text.dim() == 1 and text.is_contiguous()
+    assert table.device.type == "cpu" and table.dtype == torch.int64 and table.is_contiguous()
+    assert table.dim() == 2 and table.shape[1] == 4
+    n = table.shape[0]
+    dev = text.device
+    if status is None:
+        status = torch.empty(n, device=dev, dtype=torch.int32)
+    if table_dev is None:
+        table_dev = torch.empty(n, 4, device=dev, dtype=torch.int64)
+    assert status.dtype == torch.int32 and status.is_contiguous() and status.numel() >= n
+    assert table_dev.dtype == torch.int64 and table_dev.is_contiguous() and table_dev.numel() >= 4 * n
+    check(N.lib().snvrag_bgzf_inflate(ptr(comp), comp.numel(), ptr(table), ptr(table_dev), n, ptr(text), text.numel(),
+                                      ptr(status), stream_ptr()), "bgzf_inflate")
+    return status[:n]
+
+
+def text_last_newline(text: torch.Tensor, nbytes: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Device i64 [1]: the index of the last '\\n' in ``text[:nbytes]`` (u8, 16-byte aligned), or -1."""
+    N.require_gpu(text)
+    assert text.dtype == torch.uint8 and text.dim() == 1 and text.is_contiguous() and 0 <= nbytes <= text.numel()
+    if out is None:
+        out = torch.empty(1, device=text.device, dtype=torch.int64)
+    assert out.dtype == torch.int64 and out.numel() >= 1
+    check(N.lib().snvrag_text_last_newline(ptr(text), nbytes, ptr(out), stream_ptr()), "text_last_newline")
+    return out
+
+
 def ln_fwd_train(x: torch.Tensor, r: Optional[torch.Tensor], g: torch.Tensor, b: torch.Tensor, eps: float,
                  p_r: float = 0.0, p_out: float = 0.0, seed: int = 0, slope_x: float = 0.0, slope_r: float = 0.0):
     """(y bf16, s bf16 = act_x(x) + drop(act_r(r)) (x itself when r is None), stats f32 [M, 2]); y

@@ -76,6 +76,9 @@ def parse_args(argv=None):
     p.add_argument("--device_features", action="store_true",
                    help="build the batches on the GPU from device-resident tables (dataset/device_features.py: "
                         "DeviceBatchLoader over the same samplers); off by default, identical batches")
+    p.add_argument("--vcf_inflate", default="host", choices=["host", "device"],
+                   help="where BGZF .vcf.gz inputs are inflated: host (zlib) or device (csrc/inflate.hip, one wave "
+                        "per block); the same arrays either way, files that are not BGZF stay on the host")
     return p.parse_args(argv)
 
 
@@ -136,6 +139,8 @@ def build_data(args, rank: int, world: int):
 
 def main(argv=None):
     args = parse_args(argv)
+    from .dataset.vcf_reader import set_default_inflate
+    set_default_inflate(args.vcf_inflate)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", str(args.cuda_devices)))

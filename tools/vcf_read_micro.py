@@ -1,6 +1,7 @@
 """The VCF readers on the same seeded files in one process (GPU only).
 
   python tools/vcf_read_micro.py [SITESxSAMPLES]      default 4096x2000
+  python tools/vcf_read_micro.py --inflate [SITESxSAMPLES]     the BGZF twins: host zlib against the device inflate
 
 Writes a GT-only file (every line fixed-width) and a GT:DS:GP file (every line on the general path) from
 seeded 0/1 arrays into a local temporary directory, then times
@@ -81,8 +82,66 @@ def kernels(path, n, S, label):
     print(f"  {label}: pack rows       {t:8.3f} ms   {n * S / t / 1e6:8.1f} code GB/s   ({n * S / 1e6:.1f} MB of codes)")
 
 
+def inflate_arm(files, n, S, gt):
+    """BGZF twins (0xff00-byte blocks, level 6): read_vcf with inflate="host" first (the default path), then
+    "device", alternating for ROUNDS rounds; then the stages of the device path alone."""
+    from src import kernels as K
+    from src.dataset import bgzf, vcf_reader as V
+    ROUNDS = 4
+    for k, path in files.items():
+        p = path + ".bgzf.gz"
+        with open(path, "rb") as fh:
+            text = fh.read()
+        bgzf.write_bgzf(p, text)
+        best = {"host": None, "device": None}
+        for mode in ("host", "device"):
+            V.read_vcf(p, DEV, inflate=mode)                     # warm
+        for _ in range(ROUNDS):
+            for mode in ("host", "device"):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                vg = V.read_vcf(p, DEV, inflate=mode)
+                dt = time.perf_counter() - t0
+                best[mode] = dt if best[mode] is None else min(best[mode], dt)
+                assert vg.n_sites == n
+        assert (vg.gt() == gt).all()
+        size = os.path.getsize(p)
+        print(f"read_vcf {k:<8} BGZF {size / 1e6:7.1f} MB on disk, {len(text) / 1e6:7.1f} MB of text: inflate=host "
+              f"{best['host']:.3f} s, inflate=device {best['device']:.3f} s (best of {ROUNDS}, alternating)")
+        t0 = time.perf_counter()
+        with open(p, "rb") as fh:
+            raw = fh.read()
+        t_read = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        blocks, used = bgzf.bgzf_blocks(raw)
+        t_walk = time.perf_counter() - t0
+        assert used == len(raw)
+        out_off = np.cumsum([0] + [b.isize for b in blocks])
+        table = K.bgzf_table([b.payload_off for b in blocks], out_off[:-1], [b.payload_len for b in blocks],
+                             [b.isize for b in blocks], [b.crc for b in blocks])
+        pin = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()
+        comp = torch.empty(len(raw), device=DEV, dtype=torch.uint8)
+        t_up = events_ms(lambda: comp.copy_(pin, non_blocking=True), 5)
+        out = torch.empty((len(text) + 15) // 16 * 16, device=DEV, dtype=torch.uint8)
+        st = K.bgzf_inflate(comp, table, out)
+        assert not st.any().item() and bytes(out[:len(text)].cpu().numpy()) == text
+        status, tdev = torch.empty(len(blocks), device=DEV, dtype=torch.int32), torch.empty(len(blocks), 4, device=DEV, dtype=torch.int64)
+        t_inf = events_ms(lambda: K.bgzf_inflate(comp, table, out, status, tdev))
+        one = max(range(len(blocks)), key=lambda i: blocks[i].payload_len)       # the block with the most input
+        t_one = events_ms(lambda: K.bgzf_inflate(comp, table[one:one + 1].contiguous(), out, status, tdev))
+        nl = torch.empty(1, device=DEV, dtype=torch.int64)
+        t_nl = events_ms(lambda: K.text_last_newline(out, len(text), nl))
+        print(f"  {k}: file read {t_read * 1e3:.2f} ms, header walk of {len(blocks)} blocks {t_walk * 1e3:.2f} ms, pinned upload "
+              f"{t_up:.3f} ms, inflate + CRC kernel {t_inf:.3f} ms = {len(text) / t_inf / 1e6:.1f} text GB/s out, "
+              f"{len(raw) / t_inf / 1e6:.2f} GB/s in (the CRC is folded into the kernel), the block with the most input ({blocks[one].payload_len} -> "
+              f"{blocks[one].isize} bytes) alone {t_one:.3f} ms, last newline {t_nl:.3f} ms")
+
+
 def main():
     from src.dataset import vcf_reader as V
+    inflate = "--inflate" in sys.argv
+    if inflate:
+        sys.argv.remove("--inflate")
     n, S = (int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "4096x2000").lower().split("x"))
     rng = np.random.default_rng(0)
     gt = (rng.random((n, S, 2)) < 0.2).astype(np.int8)
@@ -98,6 +157,9 @@ def main():
         files = {"GT": os.path.join(d, "gt.vcf"), "GT:DS:GP": os.path.join(d, "gp.vcf")}
         V.write_gt_vcf(files["GT"], names, pos, gt)
         V.write_gt_vcf(files["GT:DS:GP"], names, pos, gt, fmt="GT:DS:GP", extra=":1.25:0.100,0.650,0.250")
+        if inflate:
+            inflate_arm(files, n, S, gt)
+            return
         for k in list(files):
             with open(files[k], "rb") as src, gzip.open(files[k] + ".gz", "wb", compresslevel=6) as dst:
                 dst.write(src.read())
