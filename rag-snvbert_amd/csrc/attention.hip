@@ -374,6 +374,12 @@ __device__ __forceinline__ void drop_scale_o(State& st, const AttnDrop& drop) {
     for (int qt = 0; qt < 2; ++qt) st.o[e][qt] *= drop.scale;
 }
 
+// A tile body ends on its row-sum MFMAs, and in the tail loop the next instructions are the loop
+// latch's register copies of the accumulators, in a block the tile's last block BRANCHES to: the
+// compiler pads an MFMA result's first VALU read (8 wait states here) only along the fall-through
+// order, so the copy of st.ls read the old register contents.  The drain supplies the wait states.
+__device__ __forceinline__ void mfma_drain() { asm volatile("s_nop 7" ::: "memory"); }
+
 template <bool FIRST, bool TRAIN = false>
 __device__ __forceinline__ void tile_any(const char* Kt, const char* Vt, int kbase, int L, const bf16x8 (&qf)[2],
                                          State& st, int li, int lg, const Train& tr = Train{}) {
@@ -495,7 +501,9 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
   const bf16* Kp = qkv + base + D + h * 32;
   const bf16* Vp = qkv + base + 2 * D + h * 32;
   constexpr int NW = VAR == 4 ? 8 : WAVES;          // waves per workgroup
-  constexpr int TV = VAR == 4 ? 0 : VAR;            // tile-body variant
+  constexpr int TV = VAR == 4 || VAR == 3 ? 0 : VAR;   // tile-body variant of the plain ring loop: variant 3's
+                                                        // body takes its K fragments from the caller (kin), which
+                                                        // only the ring3 loop below passes
   const int q0 = qb * (QPW * NW) + wave * QPW;
   const bool active = q0 < L;                      // wave-uniform
 
@@ -620,7 +628,10 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
       const char* Kt = smem + (t % NS) * SLOT;
       __builtin_amdgcn_s_barrier();                  // every wave done with tile t - 1 (its V)
       if (t + NS - 1 < ntile) issue(t + NS - 1, (t + NS - 1) % NS);
-      if (active) tile_any<false, TRAIN>(Kt, Kt + TB, t * KT, L, qf, st, li, lg, tr);   // t >= NS: not the first
+      if (active) {
+        tile_any<false, TRAIN>(Kt, Kt + TB, t * KT, L, qf, st, li, lg, tr);               // t >= NS: not the first
+        mfma_drain();
+      }
       ++t;
     }
   } else {
@@ -639,6 +650,7 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
       const char* Kt = smem + (t % NS) * SLOT;
       if (t == 0) tile_any<true, TRAIN>(Kt, Kt + TB, 0, L, qf, st, li, lg, tr);
       else tile_any<false, TRAIN>(Kt, Kt + TB, t * KT, L, qf, st, li, lg, tr);
+      mfma_drain();
     }
   }
   if (!active) return;

@@ -486,11 +486,18 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv32(int L, int H, const bf16* 
     for (int qt = 0; qt < 4; ++qt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float p = __builtin_amdgcn_exp2f(fmaf(s[qt][r], c_log2e, -l4[qt][r]));
-        if constexpr (MASK) p = t * 64 + 16 * qt + 4 * lg + r < L ? p : 0.f;
-        const float pm = drop.thresh ? p * mkv[qt][r] : p;
+        const float p = __builtin_amdgcn_exp2f(fmaf(s[qt][r], c_log2e, -l4[qt][r]));
+        float pm = drop.thresh ? p * mkv[qt][r] : p;
+        float ds = fmaf(pm, dp[qt][r], -p * d4[qt][r]);
+        // query rows past L are the next sequence's Q / dO rows: their S and dP may be inf or NaN,
+        // which a product with p = 0 would keep, so the results are selected, not multiplied away
+        if constexpr (MASK) {
+          const bool in = t * 64 + 16 * qt + 4 * lg + r < L;
+          pm = in ? pm : 0.f;
+          ds = in ? ds : 0.f;
+        }
         pb[qt >> 1][(qt & 1) * 4 + r] = (bf16)pm;
-        dsb[qt >> 1][(qt & 1) * 4 + r] = (bf16)fmaf(pm, dp[qt][r], -p * d4[qt][r]);
+        dsb[qt >> 1][(qt & 1) * 4 + r] = (bf16)ds;
       }
 #pragma unroll
     for (int c = 0; c < 2; ++c)
@@ -609,9 +616,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq32(int L, int H, const bf16* _
         if (drop.thresh) drop_split(drop, drop_mix24(drow + (uint32_t)(8 * kt + (r >> 1)) * DROP_C2), dm[0], dm[1]);
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          float p = __builtin_amdgcn_exp2f(fmaf(s[kt][r + e], c_log2e, -lse_q));
-          if constexpr (MASK) p = t * 64 + 16 * kt + 4 * lg + r + e < L ? p : 0.f;
-          dsb[kt >> 1][(kt & 1) * 4 + r + e] = (bf16)(p * fmaf(dp[kt][r + e], dm[e], -dq_));
+          const float p = __builtin_amdgcn_exp2f(fmaf(s[kt][r + e], c_log2e, -lse_q));
+          float ds = p * fmaf(dp[kt][r + e], dm[e], -dq_);
+          // keys past L are the next sequence's K / V rows: their S and dP may be inf or NaN, which
+          // a product with p = 0 would keep, so dS is selected, not multiplied away
+          if constexpr (MASK) ds = t * 64 + 16 * kt + 4 * lg + r + e < L ? ds : 0.f;
+          dsb[kt >> 1][(kt & 1) * 4 + r + e] = (bf16)ds;
         }
       }
 #pragma unroll

@@ -207,3 +207,66 @@ def test_gemm256_no_write_or_read_before_asm_load_lands(tmp_path):
         bad = _pending_writes(ins) + _pending_reads(ins)
         assert not bad, (name, bad[:5])
 
+
+
+def _mfma_result_used_early(text, raw=8, waw=7):
+    """(mfma, instruction, wait states) of every non-MFMA instruction that reads an MFMA's destination
+    registers fewer than ``raw`` wait states after it, or overwrites them fewer than ``waw`` after it,
+    along ANY path: fall-through and the targets of the branches on the way."""
+    items = [ln.split(";")[0].strip() for ln in text]
+    items = [ln for ln in items if ln and (ln.startswith(".LBB") or not ln.startswith((".", "_")))]
+    label = {ln[:-1]: i for i, ln in enumerate(items) if ln.endswith(":")}
+    bad, n_mfma = [], 0
+    for i, t in enumerate(items):
+        if not t.startswith("v_mfma"):
+            continue
+        n_mfma += 1
+        dst = _regs(t.split()[1].rstrip(","))
+        stack, seen = [(i + 1, 0)], set()
+        while stack:
+            k, ws = stack.pop()
+            while k < len(items) and ws < raw and (k, ws) not in seen:
+                seen.add((k, ws))
+                u = items[k]
+                op = u.split()[0]
+                if u.endswith(":"):
+                    k += 1
+                    continue
+                if op == "s_endpgm":
+                    break
+                if op == "s_nop":
+                    ws += int(u.split()[1]) + 1
+                    k += 1
+                    continue
+                if op.startswith("s_cbranch") or op == "s_branch":
+                    if u.split()[1] in label:
+                        stack.append((label[u.split()[1]], ws + 1))
+                    if op == "s_branch":
+                        break
+                elif not op.startswith("v_mfma") and op.startswith(("v_", "ds_", "buffer_", "global_")) and " " in u:
+                    ops = [o.strip().split()[0] for o in u.split(None, 1)[1].split(",") if o.strip()]
+                    if (_reads(u) & dst) or (ws < waw and ops and _regs(ops[0]) & dst):
+                        bad.append((t, u, ws))
+                        break
+                ws += 1
+                k += 1
+    return bad, n_mfma
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
+@pytest.mark.parametrize("src", ["attention.hip", "attention_train.hip"])
+def test_attention_no_mfma_result_used_across_a_branch_inside_its_latency(tmp_path, src):
+    """The attention kernels' MFMAs are builtins, which the compiler pads itself -- along the
+    fall-through order: 8 wait states before a VALU read of the result, 7 before an overwrite.  A
+    tile body that ends on an MFMA and then BRANCHES to the loop latch's register copies (placed
+    earlier in the text) got no padding: the copy of the last row-sum accumulator read the old
+    register contents, for some code alignments only (wrong row sums of eight queries in
+    attn32_dma's tail loop).  Every path out of every MFMA is walked here with the compiler's own
+    two distances."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    out = tmp_path / "a.s"
+    subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-mllvm", "-amdgpu-mfma-vgpr-form=1", "-S",
+                    "--cuda-device-only", os.path.join(CSRC, src), "-o", str(out)], check=True, capture_output=True)
+    bad, n_mfma = _mfma_result_used_early(out.read_text().split("\n"))
+    assert n_mfma > 300
+    assert not bad, (len(bad), bad[:5])
