@@ -11,66 +11,27 @@
 // 4 waves (one per SIMD, 512 registers), wave w: rows 64 w .. 64 w + 63 as two 32-token groups.
 // Every MFMA (v_mfma_f32_32x32x16_bf16) computes a TRANSPOSED tile — 32 weight rows (A operand, a
 // 1 KiB fragment read from LDS) x 32 tokens (B operand) — so a lane ends up holding 16 consecutive
-// output features of one token (the weight rows are permuted at pack time, g2_out_feat), stored as
+// output features of one token (the weight rows are permuted at pack time, out_feat), stored as
 // two 16-B pieces.  Per K-step of 64 the LDS ring streams 2 + NT / 4 slabs of 16 KiB by LDS-DMA:
 // A0, A1 (the 256 rows x 128 B of A: 8 whole 128-B lines per DMA instruction, 16-B chunks XOR-
 // swizzled by row & 7 so the B-fragment reads are conflict-free), then the K-step's W fragments in
 // consumption order (k16 step s, feature tile T).  One barrier per slab, counted vmcnt (inline-asm
 // DMA: the compiler sees no LDS stores), 7 slabs in flight.
 #include "common.h"
-
-#include <utility>
+#include "mfma32.h"
 
 namespace snvrag {
 
-constexpr int G2_FRAG = 1024;
-constexpr int G2_SLAB = 16 * G2_FRAG;
 constexpr int G2_NSLOT = 9;
 constexpr int G2_ROWS = 256;
 constexpr int G2_PF = 4;
-constexpr int G2_NACC = 16;                          // accumulator tiles in AGPRs
+// 384 accumulator registers per lane: the first G2_NACC tiles live in AGPRs, the rest in VGPRs
+// (mfma32_asm, without its s_nop: nothing here writes an MFMA operand right before it)
+constexpr int G2_NACC = 16;
 
-// weight row held by MFMA row m of feature tile T: lane (token, hh) then holds features
-// 32 T + 16 hh + i in accumulator element i
-__host__ __device__ constexpr int g2_out_feat(int T, int m) {
-  return 32 * T + 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3);
-}
-
-template <typename Body, int... Is>
-__device__ __forceinline__ void g2_unroll(Body&& body, std::integer_sequence<int, Is...>) {
-  (body(std::integral_constant<int, Is>{}), ...);
-}
-
-// 384 accumulator registers per lane: the first G2_NACC tiles live in AGPRs, the rest in VGPRs.
-// The MFMA is inline asm so that the register class of every accumulator is fixed (the builtin's
-// single AGPR-or-VGPR form for the whole kernel spills half of them); the compiler then does not
-// know these are MFMAs, so nothing may read an accumulator within 18 wait states of its last MFMA
-// unless g2_drain runs in between — including the compiler's own register moves (see g3_kernel).
-template <bool AGPR>
-__device__ __forceinline__ void g2_mfma(f32x16& c, const u32x4& a, const u32x4& b) {
-  if constexpr (AGPR)
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-  else
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-// 32x32 MFMA (16 passes): a result is readable 18 wait states after issue
-__device__ __forceinline__ void g2_drain() { asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory"); }
-
-// lane id produced afresh at each use (not kept live across the K loop)
-__device__ __forceinline__ int g2_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
 __device__ __forceinline__ int g2_opq(int v) {
   asm volatile("" : "+s"(v));
   return v;
-}
-__device__ __forceinline__ uint32_t g2_pack2(float a, float b) {
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  const f2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, b2));
 }
 
 struct G2Args {
@@ -97,11 +58,6 @@ struct G2Args {
   int desync;                // g3: > 0, first-round stagger step in cycles (multi-round launches)
 };
 
-__device__ __forceinline__ float g2_maf_w(float af) {   // fusion.py:155-160
-  const float maf = fminf(af, 1.0f - af);
-  return fminf(log1pf(1.0f / (maf + 1e-6f)), 3.0f);
-}
-
 template <int NT, int VAR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void g2_kernel(G2Args p) {
@@ -110,7 +66,7 @@ void g2_kernel(G2Args p) {
   static_assert(FPK % 16 == 0, "whole W slabs per K-step");
   constexpr int WS = FPK / 16;                        // W slabs per K-step
   constexpr int SPK = 2 + WS;                         // slabs per K-step: A0, A1, W ...
-  constexpr int RING = G2_NSLOT * G2_SLAB;
+  constexpr int RING = G2_NSLOT * SLAB_BYTES;
   constexpr int AHEAD = G2_NSLOT - 2;                 // sync(g) issues slab g + AHEAD
   constexpr int VM = 4 * (G2_NSLOT - 3);
   static_assert(VM <= 63, "vmcnt range");
@@ -137,15 +93,15 @@ void g2_kernel(G2Args p) {
   // ---- issue side: slab (K-step kt, position r) into ring slot is_slot
   const long a_bytes = ((long)M - row0) * p.lda * 2;
   const i32x4 ars = dma_rsrc(p.A + row0 * p.lda, a_bytes);      // rows >= M read as zeros
-  const i32x4 wrs = dma_rsrc(p.ws, (long)nk * WS * G2_SLAB);
-  const uint32_t ring_lds = lds_addr(ring) + wave * 4 * G2_FRAG;
+  const i32x4 wrs = dma_rsrc(p.ws, (long)nk * WS * SLAB_BYTES);
+  const uint32_t ring_lds = lds_addr(ring) + wave * 4 * FRAG_BYTES;
   int is_slot = 0;
   // per-lane offsets kept in two VGPRs for the whole kernel: the lane's 16 B of a fragment, and the
   // lane's piece of an A slab (row 32 w + l / 8 of the slab, swizzled chunk)
-  int lane16 = g2_lane() * 16;
+  int lane16 = lane_id() * 16;
   int voffA;
   {
-    const int l = g2_lane(), row = 32 * wave + (l >> 3);
+    const int l = lane_id(), row = 32 * wave + (l >> 3);
     voffA = (int)(row * p.lda * 2) + 16 * ((l & 7) ^ ((l >> 3) & 7));
   }
   asm volatile("" : "+v"(lane16), "+v"(voffA));
@@ -153,19 +109,19 @@ void g2_kernel(G2Args p) {
   auto put = [&](int r, int kt) {                     // r, kt wave-uniform; r compile-time at every call
     const int lds = (int)g2_opq((int)ring_lds) + is_slot;
     if constexpr (VAR == 1) {                         // diagnostic: no loads
-      is_slot = is_slot + G2_SLAB == RING ? 0 : is_slot + G2_SLAB;
+      is_slot = is_slot + SLAB_BYTES == RING ? 0 : is_slot + SLAB_BYTES;
       return;
     }
     if (r < 2) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        dma_x4(ars, lds + j * G2_FRAG, voffA + (int)((128 * r + 8 * j) * p.lda * 2), 128 * kt);
+        dma_x4(ars, lds + j * FRAG_BYTES, voffA + (int)((128 * r + 8 * j) * p.lda * 2), 128 * kt);
     } else {
-      const int so = ((kt * WS + r - 2) * 16 + 4 * g2_opq(wave)) * G2_FRAG;
+      const int so = ((kt * WS + r - 2) * 16 + 4 * g2_opq(wave)) * FRAG_BYTES;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) dma_x4(wrs, lds + j * G2_FRAG, lane16, so + j * G2_FRAG);
+      for (int j = 0; j < 4; ++j) dma_x4(wrs, lds + j * FRAG_BYTES, lane16, so + j * FRAG_BYTES);
     }
-    is_slot = is_slot + G2_SLAB == RING ? 0 : is_slot + G2_SLAB;
+    is_slot = is_slot + SLAB_BYTES == RING ? 0 : is_slot + SLAB_BYTES;
   };
   // the target of a sync at K-step k, position R (compile-time): slab (k, R) + AHEAD
   auto issue = [&](auto r_tag, int k) {
@@ -177,7 +133,7 @@ void g2_kernel(G2Args p) {
   };
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // bias table loads retired
   __syncthreads();
-  g2_unroll([&](auto qc) {
+  unroll([&](auto qc) {
     constexpr int q = decltype(qc)::value;
     put(q % SPK, q / SPK < nk ? q / SPK : nk - 1);
   }, std::make_integer_sequence<int, AHEAD>{});
@@ -192,21 +148,21 @@ void g2_kernel(G2Args p) {
   // ---- read side
   int rd_slot = 0;
   auto adv = [&](int n) {
-    rd_slot += n * G2_SLAB;
+    rd_slot += n * SLAB_BYTES;
     rd_slot = rd_slot >= RING ? rd_slot - RING : rd_slot;
   };
   auto rdA = [&](auto j_tag, auto fi_tag) -> u32x4 {  // W fragment fi of slab j of the current part
     constexpr int j = decltype(j_tag)::value, fi = decltype(fi_tag)::value;
-    int so = rd_slot + j * G2_SLAB;
+    int so = rd_slot + j * SLAB_BYTES;
     so = so >= RING ? so - RING : so;
-    return *reinterpret_cast<const u32x4*>(ring + so + lane16 + fi * G2_FRAG);
+    return *reinterpret_cast<const u32x4*>(ring + so + lane16 + fi * FRAG_BYTES);
   };
   // B fragment (token group g, k16 step s) of this wave's rows from the K-step's A slabs (A0 at
   // the current rd_slot): row 64 w + 32 g + n lies in slab w / 2
   auto rdB = [&](int g, int s) -> u32x4 {
-    const int l = g2_lane();
+    const int l = lane_id();
     const int rs = (64 * g2_opq(wave) + 32 * g + (l & 31)) & 127;
-    int so = rd_slot + (g2_opq(wave) >> 1) * G2_SLAB;
+    int so = rd_slot + (g2_opq(wave) >> 1) * SLAB_BYTES;
     so = so >= RING ? so - RING : so;
     const int c = 2 * s + (l >> 5);
     return *reinterpret_cast<const u32x4*>(ring + so + rs * 128 + 16 * (c ^ (rs & 7)));
@@ -240,9 +196,9 @@ void g2_kernel(G2Args p) {
     if constexpr (VAR == 3) st_b += __builtin_amdgcn_s_memtime() - tb0;
     adv(2);
     sync(R2{}, k);                                     // the first W slab
-    g2_unroll([&](auto ic) { a[decltype(ic)::value] = rdA(R0{}, ic); }, std::make_integer_sequence<int, G2_PF>{});
+    unroll([&](auto ic) { a[decltype(ic)::value] = rdA(R0{}, ic); }, std::make_integer_sequence<int, G2_PF>{});
     // FPK fragments: fragment f = s NT + T feeds both token groups; one sync per slab, PF ahead
-    g2_unroll([&](auto fc) {
+    unroll([&](auto fc) {
       constexpr int f = decltype(fc)::value;
       const u32x4 cur = a[f % G2_PF];
       if constexpr ((f & 15) == 16 - G2_PF) {
@@ -252,8 +208,8 @@ void g2_kernel(G2Args p) {
       }
       constexpr int s = f / NT, T = f % NT;
       if constexpr (VAR != 2) {
-        g2_mfma<true>(acc[0][T], cur, bf[0][s]);
-        g2_mfma<(NT + T < G2_NACC)>(acc[1][T], cur, bf[1][s]);
+        mfma32_asm<true, false>(acc[0][T], cur, bf[0][s]);
+        mfma32_asm<(NT + T < G2_NACC), false>(acc[1][T], cur, bf[1][s]);
       } else {
         asm volatile("" ::"v"(cur), "v"(bf[0][s]), "v"(bf[1][s]));
       }
@@ -264,7 +220,7 @@ void g2_kernel(G2Args p) {
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
     }, std::make_integer_sequence<int, FPK>{});
     adv(WS);
-    if (k == nk - 1) g2_drain();                      // (inside the loop: see g3_kernel)
+    if (k == nk - 1) drain();                      // (inside the loop: see g3_kernel)
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the ring overrun has landed
   stamp(3, __builtin_amdgcn_s_memtime());
@@ -283,7 +239,7 @@ void g2_kernel(G2Args p) {
   const bool has_res = p.resid != nullptr;
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
-    const int l = g2_lane();
+    const int l = lane_id();
     const int rl = 64 * wave + 32 * g + (l & 31);     // row within the workgroup's tile
     const int hh = l >> 5;
 #pragma unroll
@@ -305,16 +261,16 @@ void g2_kernel(G2Args p) {
           const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rrs, (int)(rl * p.ld_resid + f0 + 8 * h2) * 2, 0, 0);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            y[8 * h2 + 2 * e] += __uint_as_float(r[e] << 16);
-            y[8 * h2 + 2 * e + 1] += __uint_as_float(r[e] & 0xffff0000u);
+            y[8 * h2 + 2 * e] += bf_lo(r[e]);
+            y[8 * h2 + 2 * e + 1] += bf_hi(r[e]);
           }
         }
       }
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2)
         __builtin_amdgcn_raw_buffer_store_b128(
-            u32x4{g2_pack2(y[8 * h2], y[8 * h2 + 1]), g2_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                  g2_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), g2_pack2(y[8 * h2 + 6], y[8 * h2 + 7])},
+            u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                  pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])},
             ors, (int)(rl * p.ldo + f0 + 8 * h2) * 2, 0, 0);
     }
   }
@@ -360,11 +316,7 @@ void g3_kernel(G2Args p) {
     if constexpr (VAR == 3)
       if ((threadIdx.x & 63) == 0) p.stamps[((long)blockIdx.x * 4 + wave) * 8 + i] = v;
   };
-  if (p.desync > 0 && blockIdx.x < 256) {             // first-round stagger (sg_kernel's)
-    const long wait = (long)p.desync * ((blockIdx.x >> 3) & 7);
-    const long t0 = (long)__builtin_amdgcn_s_memtime();
-    while ((long)__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(16);
-  }
+  if (p.desync > 0 && blockIdx.x < 256) stagger_wait(p.desync);   // first-round stagger (mfma32.h)
   stamp(0, __builtin_amdgcn_s_memtime());
   stamp(1, __builtin_amdgcn_s_memrealtime());
   const long row0 = (long)blockIdx.x * (32 * G);
@@ -376,14 +328,14 @@ void g3_kernel(G2Args p) {
     }
 
   const i32x4 ars = dma_rsrc(p.A + row0 * p.lda, ((long)M - row0) * p.lda * 2);   // rows >= M read as 0
-  const i32x4 wrs = dma_rsrc(p.ws, (long)nk * 4 * 12 * G2_FRAG);
+  const i32x4 wrs = dma_rsrc(p.ws, (long)nk * 4 * 12 * FRAG_BYTES);
   const uint32_t img_lds = lds_addr(smem);
   // per-lane offsets (VGPRs for the whole kernel): the lane's 16 B of a fragment; its piece of an A
   // image (row l / 8 of the piece, swizzled chunk); its B-fragment bytes per k16 step s (row n,
   // chunk 2 s + kh stored at (2 s + kh) ^ (n % 8))
   int lane16, voffA, boff[4];
   {
-    const int l = g2_lane(), n = l & 31, kh = l >> 5;
+    const int l = lane_id(), n = l & 31, kh = l >> 5;
     lane16 = l * 16;
     voffA = (int)((l >> 3) * p.lda * 2) + 16 * ((l & 7) ^ ((l >> 3) & 7));
 #pragma unroll
@@ -395,10 +347,10 @@ void g3_kernel(G2Args p) {
   auto putA = [&](int slot, int j, int kt) {
     if constexpr (VAR == 1) return;                   // diagnostic: no A loads
     const int pc = G * g2_opq(wave) + j;
-    dma_x4(ars, img_lds + slot + pc * G2_FRAG, voffA + (int)(8 * pc * p.lda * 2), 128 * kt);
+    dma_x4(ars, img_lds + slot + pc * FRAG_BYTES, voffA + (int)(8 * pc * p.lda * 2), 128 * kt);
   };
   auto loadW = [&](u32x4& w, int kt, int s, int t) {
-    const int so = ((4 * kt + s) * 12 + 3 * g2_opq(wave) + t) * G2_FRAG;
+    const int so = ((4 * kt + s) * 12 + 3 * g2_opq(wave) + t) * FRAG_BYTES;
     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(w) : "v"(lane16), "s"(wrs), "s"(so) : "memory");
   };
 
@@ -432,7 +384,7 @@ void g3_kernel(G2Args p) {
     auto rdB = [&](int i) -> u32x4 {                  // B fragment i = G s + g of this K-step
       return *reinterpret_cast<const u32x4*>(smem + slot_rd + boff[i / G] + (i % G) * 4096);
     };
-    g2_unroll([&](auto sc) {
+    unroll([&](auto sc) {
       constexpr int s = decltype(sc)::value;
       if constexpr (VAR == 3) st_t = __builtin_amdgcn_s_memtime();
       asm volatile("s_waitcnt vmcnt(%3)" : "+v"(w[s][0]), "+v"(w[s][1]), "+v"(w[s][2])
@@ -443,15 +395,15 @@ void g3_kernel(G2Args p) {
         for (int i = 0; i < G3_PF; ++i) bq[i] = rdB(i);
       }
       if constexpr (VAR == 3) st_wait += __builtin_amdgcn_s_memtime() - st_t;
-      g2_unroll([&](auto gc) {
+      unroll([&](auto gc) {
         constexpr int g = decltype(gc)::value, i = G * s + g;
         const u32x4 b = bq[i % G3_PF];
         if constexpr (i + G3_PF < 4 * G) bq[i % G3_PF] = rdB(i + G3_PF);
 #pragma unroll
         for (int t = 0; t < TW; ++t) {
           if constexpr (VAR != 2) {
-            if (g * TW + t < G2_NACC) g2_mfma<true>(acc[g][t], w[s][t], b);
-            else g2_mfma<false>(acc[g][t], w[s][t], b);
+            if (g * TW + t < G2_NACC) mfma32_asm<true, false>(acc[g][t], w[s][t], b);
+            else mfma32_asm<false, false>(acc[g][t], w[s][t], b);
           } else {
             asm volatile("" ::"v"(w[s][t]), "v"(b));
           }
@@ -480,7 +432,7 @@ void g3_kernel(G2Args p) {
                    : "+v"(w[0][0]), "+v"(w[0][1]), "+v"(w[0][2]), "+v"(w[1][0]), "+v"(w[1][1]), "+v"(w[1][2]),
                      "+v"(w[2][0]), "+v"(w[2][1]), "+v"(w[2][2]), "+v"(w[3][0]), "+v"(w[3][1]), "+v"(w[3][2])
                    :: "memory");
-      g2_drain();
+      drain();
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the A overrun DMA has landed
@@ -496,7 +448,7 @@ void g3_kernel(G2Args p) {
     // are spread over the 4 waves: per-wave partial sums through LDS, summed in wave order); then
     // out = base + post_scale * (LN(y) g + be) * w(af[row % period]) -> bf16
     float* red = sb + 3 * N;                          // [4 waves][G][32]
-    const int n = g2_lane() & 31, hh = g2_lane() >> 5;
+    const int n = lane_id() & 31, hh = lane_id() >> 5;
     auto tile_vec = [&](const float* tab, int t, u32x4 (&v)[4]) {
       const uint32_t ba = lds_addr(tab) + 4 * (96 * wave + 32 * t + 16 * hh);
       asm volatile(
@@ -555,7 +507,7 @@ void g3_kernel(G2Args p) {
       rstd[g] = 1.0f / sqrtf(rstd[g] * (1.0f / N) + p.ln_eps);
       long m = row0 + 32 * g + n;
       m = m < M ? m : M - 1;
-      w[g] = p.post_af ? g2_maf_w(p.post_af[p.post_af_period > 0 ? m % p.post_af_period : m]) : 1.0f;
+      w[g] = p.post_af ? maf_w(p.post_af[p.post_af_period > 0 ? m % p.post_af_period : m]) : 1.0f;
     }
     const long b_bytes = p.base ? rows_left * p.ld_base * 2 : 0;
     const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(
@@ -586,12 +538,12 @@ void g3_kernel(G2Args p) {
             const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(brs, (int)(rl * p.ld_base + f0) * 2, 0, 0);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              y[2 * e] = __uint_as_float(r[e] << 16) + p.post_scale * (y[2 * e] * w[g]);
-              y[2 * e + 1] = __uint_as_float(r[e] & 0xffff0000u) + p.post_scale * (y[2 * e + 1] * w[g]);
+              y[2 * e] = bf_lo(r[e]) + p.post_scale * (y[2 * e] * w[g]);
+              y[2 * e + 1] = bf_hi(r[e]) + p.post_scale * (y[2 * e + 1] * w[g]);
             }
           }
           __builtin_amdgcn_raw_buffer_store_b128(
-              u32x4{g2_pack2(y[0], y[1]), g2_pack2(y[2], y[3]), g2_pack2(y[4], y[5]), g2_pack2(y[6], y[7])},
+              u32x4{pack2(y[0], y[1]), pack2(y[2], y[3]), pack2(y[4], y[5]), pack2(y[6], y[7])},
               ors, (int)(rl * p.ldo + f0) * 2, 0, 0);
         }
       }
@@ -607,7 +559,7 @@ void g3_kernel(G2Args p) {
   const bool has_res = p.resid != nullptr;
 #pragma unroll
   for (int t = 0; t < TW; ++t) {
-    const int l = g2_lane();
+    const int l = lane_id();
     const int f0 = 96 * wave + 32 * t + 16 * (l >> 5);
     u32x4 bv[4];
     asm volatile(
@@ -617,7 +569,7 @@ void g3_kernel(G2Args p) {
         : "v"(lds_addr(sb) + 4 * f0));
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-      const int rl = 32 * g + (g2_lane() & 31);
+      const int rl = 32 * g + (lane_id() & 31);
       float y[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) y[i] = acc[g][t][i] + __uint_as_float(bv[i >> 2][i & 3]);
@@ -627,16 +579,16 @@ void g3_kernel(G2Args p) {
           const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rrs, (int)(rl * p.ld_resid + f0 + 8 * h2) * 2, 0, 0);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            y[8 * h2 + 2 * e] += __uint_as_float(r[e] << 16);
-            y[8 * h2 + 2 * e + 1] += __uint_as_float(r[e] & 0xffff0000u);
+            y[8 * h2 + 2 * e] += bf_lo(r[e]);
+            y[8 * h2 + 2 * e + 1] += bf_hi(r[e]);
           }
         }
       }
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2)
         __builtin_amdgcn_raw_buffer_store_b128(
-            u32x4{g2_pack2(y[8 * h2], y[8 * h2 + 1]), g2_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                  g2_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), g2_pack2(y[8 * h2 + 6], y[8 * h2 + 7])},
+            u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                  pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])},
             ors, (int)(rl * p.ldo + f0 + 8 * h2) * 2, 0, 0);
     }
   }
@@ -649,8 +601,7 @@ static int g3_launch(G2Args a, hipStream_t s) {
   auto kern = g3_kernel<G, VAR, EPI>;
   // first-round stagger for multi-round launches (r6, tools/g3_desync_sweep.py, the rag fusion's
   // K = 4D projection at M = 527 360: 10 k cycles 0.929 vs 0.961 ms; training's one-round launches none)
-  const int64_t dz = options().g2_desync;
-  a.desync = cdiv(a.M, 32 * G) >= 4 * 256 ? (dz >= 0 ? (int)dz : 10000) : 0;
+  a.desync = stagger_step(cdiv(a.M, 32 * G), 4 * 256, options().g2_desync, 10000);
   // + bias table (+ EPI 1: LN g, be tables and the [4][G][32] row-sum exchange)
   constexpr size_t lds = (size_t)G3_NS * g3_img(G) + 384 * 4 + (EPI == 1 ? 2 * 384 * 4 + 4 * G * 32 * 4 : 0);
   static_assert(lds <= 160 * 1024, "LDS budget");
@@ -694,23 +645,19 @@ static int g3_groups(long M) {
   return G;
 }
 
-// One thread per 16-byte piece: fragment F = k16 NT + T, lane l = (m = l % 32, kh = l / 32) holds
-// W[g2_out_feat(T, m)][16 k16 + 8 kh + j], j < 8 (W bf16 [N, K] row-major, leading dim ldw)
+// One thread per 16-byte piece, in gemm256_piece_src's order (mfma32.h); W bf16 [N, K] row-major,
+// leading dim ldw
 __global__ void g2_pack_kernel(int NT, long n_pieces, const bf16* __restrict__ w, long ldw, bf16* __restrict__ out) {
   const long pc = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (pc >= n_pieces) return;
-  const long F = pc / 64;
-  const int l = (int)(pc % 64), m = l & 31, kh = l >> 5;
-  const long k16 = F / NT;
-  const int T = (int)(F % NT);
-  const long n = g2_out_feat(T, m);
-  for (int j = 0; j < 8; ++j) out[pc * 8 + j] = w[n * ldw + 16 * k16 + 8 * kh + j];
+  const PieceSrc q = gemm256_piece_src(NT, pc);
+  for (int j = 0; j < 8; ++j) out[pc * 8 + j] = w[q.row * ldw + q.col + j];
 }
 
 template <int NT, int VAR>
 static int g2_launch(const G2Args& a, hipStream_t s) {
   auto kern = g2_kernel<NT, VAR>;
-  constexpr size_t lds = (size_t)G2_NSLOT * G2_SLAB + 32 * NT * 4;
+  constexpr size_t lds = (size_t)G2_NSLOT * SLAB_BYTES + 32 * NT * 4;
   static_assert(lds <= 160 * 1024, "LDS budget");
   SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, G2_ROWS)), dim3(256), lds, s, a);

@@ -20,6 +20,7 @@
 // c1 = W gamma and beta folded into the bias (feed_forward.py:20, w_2(norm(x)),
 // without ever materialising norm(x)); mean/rstd from the producer's row stats.
 #include "common.h"
+#include "mfma32.h"   // maf_w
 
 namespace snvrag {
 
@@ -77,11 +78,6 @@ __device__ __forceinline__ void store8(bf16* p, const float* v) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) a[e] = (bf16)v[e];
   *reinterpret_cast<bf16x8*>(p) = a;
-}
-
-__device__ __forceinline__ float maf_w(float af) {
-  const float maf = fminf(af, 1.0f - af);
-  return fminf(log1pf(1.0f / (maf + 1e-6f)), 3.0f);
 }
 
 // 128-B K-tile rows, 2 LDS stages: the next tile's global_load_lds in flight under this tile's

@@ -11,7 +11,7 @@
 // foundation_model.py:64-80 (af_fusion[0] over cat(x, af, af_p) + GELU; net[0] + GELU + net[2]
 // + softmax).
 //
-// The block tail's machinery (tail.hip) with the output tiles OUTERMOST: a workgroup owns 128
+// The block tail's machinery (tail.hip, mfma32.h) with the output tiles OUTERMOST: a workgroup owns 128
 // token rows (4 waves x 32, one wave per SIMD), x stays in VGPRs as B fragments for the whole
 // launch, W streams once per workgroup through an 8-slot ring of 16 KiB LDS slabs by LDS-DMA
 // (buffer_load ... lds, counted vmcnt, one barrier per slab).  The stream is ordered by pairs
@@ -22,36 +22,15 @@
 // accumulators (64 registers) instead of N / 32 x 16.  Workgroups start at rotated pairs
 // (blockIdx % pairs) so concurrent workgroups read different stream offsets.
 #include "common.h"
-
-#include <utility>
+#include "mfma32.h"
 
 namespace snvrag {
 
-constexpr int SG_FRAG = 1024;              // one A fragment: 32 W rows x 16 k (bf16)
-constexpr int SG_SLAB = 16 * SG_FRAG;
 constexpr int SG_NSLOT = 8;                // ring slots (128 KiB)
 constexpr int SG_PF = 4;                   // A fragments read ahead
 constexpr int SG_VEC_BYTES = 24 * 1024;    // f32 vector table in LDS
 enum { SG_ACT = 0, SG_HEAD2 = 1, SG_LN = 2 };
 
-// feature permutations shared with tail.hip: MFMA row m of an output tile is feature
-// 16((m/4)%2) + 4(m/8) + m%4, so lane (n, hh) holds features 16hh + i (i < 16) of its tile; the
-// k order of x's B fragments and W's columns: k-step s, lane half kh, element j
-__host__ __device__ constexpr int sg_out_feat(int m) { return 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3); }
-__host__ __device__ constexpr int sg_in_feat(int s, int kh, int j) { return 32 * (s >> 1) + 16 * kh + 8 * (s & 1) + j; }
-
-__device__ __forceinline__ f32x16 sg_mfma(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-typedef __bf16 sg_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float sg_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t sg_pack2(float a, float b) {          // one v_cvt_pk_bf16_f32
-  const sg_f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, sg_bf16x2));
-}
-__device__ __forceinline__ uint32_t sg_lds(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
 // LDS reads of the vector table: the reads and their wait in ONE asm statement (a compiler LDS
 // read here would wait for the whole in-flight weight stream).
 // the 8 x 4 floats of one tile PAIR this lane needs from a table at LDS byte address `a` (its
@@ -63,10 +42,6 @@ __device__ __forceinline__ void sg_vec8(uint32_t a, u32x4 (&v)[8]) {
       " ds_read_b128 %6, %8 offset:160\n ds_read_b128 %7, %8 offset:176\n s_waitcnt lgkmcnt(0)"
       : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
       : "v"(a));
-}
-template <typename Body, int... Is>
-__device__ __forceinline__ void sg_unroll(Body&& body, std::integer_sequence<int, Is...>) {
-  (body(std::integral_constant<int, Is>{}), ...);
 }
 template <int ACT> __device__ __forceinline__ float sg_act(float x, float slope) {
   if constexpr (ACT == SNVRAG_ACT_GELU) return gelu_bf16(x);
@@ -87,7 +62,7 @@ struct SgArgs {
   // CAT: x = [q | bf16(x2 * g2[m % period2])], q = `x` and x2 [M, D/2], g2 [period2, D/2] (fusion.py:157:
   // cat(h, aw * h_rag) built in registers)
   const bf16* x2; const bf16* g2; int period2;
-  int desync;               // > 0: first-round phase step in cycles (tail.hip's de-synchronised rounds)
+  int desync;               // > 0: first-round phase step in cycles (stagger_wait, mfma32.h)
 };
 
 template <int EPI, bool RANK> __host__ __device__ constexpr int sg_nvec(int N) {
@@ -102,7 +77,7 @@ void sg_kernel(SgArgs p) {
   constexpr int KS = D / 16, NT = D / 32, FPP = 2 * KS;           // fragments per tile pair
   static_assert(FPP % 16 == 0, "pairs are whole slabs");
   constexpr int SPP = FPP / 16;                                    // slabs per pair
-  constexpr int RING = SG_NSLOT * SG_SLAB;
+  constexpr int RING = SG_NSLOT * SLAB_BYTES;
   constexpr int NTH = 64 * WAVES, ROWS = 32 * WAVES, PPW = 16 / WAVES;   // pieces per wave per slab
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem;
@@ -113,13 +88,7 @@ void sg_kernel(SgArgs p) {
   const int N = p.N, NP = N / 64;                                  // tile pairs
   const long row = (long)blockIdx.x * ROWS + wave * 32 + ln;
   const long rc = row < p.M ? row : (long)p.M - 1;
-  // first-round workgroups start at 8 phase offsets (see tail.hip): later rounds' activation
-  // loads and output stores then stop hitting HBM as one chip-wide burst
-  if (p.desync > 0 && blockIdx.x < 256) {
-    const long wait = (long)p.desync * ((blockIdx.x >> 3) & 7);
-    const long t0 = (long)__builtin_amdgcn_s_memtime();
-    while ((long)__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(16);
-  }
+  if (p.desync > 0 && blockIdx.x < 256) stagger_wait(p.desync);   // first-round stagger (mfma32.h)
 
   // ---- vector table -> LDS, x -> B fragments, rank scalars: all plain loads retire before the
   // DMA ring starts (its waits are counted)
@@ -130,20 +99,19 @@ void sg_kernel(SgArgs p) {
     constexpr int DH = D / 2;
     const long rg = rc % p.period2;
 #pragma unroll
-    for (int s = 0; s < KS / 2; ++s) xa[s] = *reinterpret_cast<const u32x4*>(p.x + rc * DH + sg_in_feat(s, hh, 0));
+    for (int s = 0; s < KS / 2; ++s) xa[s] = *reinterpret_cast<const u32x4*>(p.x + rc * DH + in_feat(s, hh, 0));
 #pragma unroll
     for (int s = KS / 2; s < KS; ++s) {
-      const int f = sg_in_feat(s, hh, 0) - DH;
+      const int f = in_feat(s, hh, 0) - DH;
       const u32x4 r = *reinterpret_cast<const u32x4*>(p.x2 + rc * DH + f);
       const u32x4 g = *reinterpret_cast<const u32x4*>(p.g2 + rg * DH + f);
 #pragma unroll
       for (int w = 0; w < 4; ++w)           // bf16(r * g) per element, as rag_concat rounds it
-        xa[s][w] = sg_pack2(__uint_as_float(r[w] << 16) * __uint_as_float(g[w] << 16),
-                            __uint_as_float(r[w] & 0xffff0000u) * __uint_as_float(g[w] & 0xffff0000u));
+        xa[s][w] = pack2(bf_lo(r[w]) * bf_lo(g[w]), bf_hi(r[w]) * bf_hi(g[w]));
     }
   } else {
 #pragma unroll
-    for (int s = 0; s < KS; ++s) xa[s] = *reinterpret_cast<const u32x4*>(p.x + rc * D + sg_in_feat(s, hh, 0));
+    for (int s = 0; s < KS; ++s) xa[s] = *reinterpret_cast<const u32x4*>(p.x + rc * D + in_feat(s, hh, 0));
   }
   float r1v = 0.f, r2v = 0.f;
   if constexpr (RANK) {
@@ -157,21 +125,21 @@ void sg_kernel(SgArgs p) {
   // (LN keeps every tile in a compile-time indexed register array: stream order, no rotation)
   const int rot = EPI == SG_LN ? 0 : (int)(blockIdx.x % NP);
   const int nslab = NP * SPP;
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, nslab * SG_SLAB, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, nslab * SLAB_BYTES, 0x00020000);
   const int voff = lane * 16;
   int is_slot = 0, is_i = 0;
   auto issue_next = [&]() {
-    auto* dst = (__attribute__((address_space(3))) char*)(ring + is_slot + wave * PPW * SG_FRAG);
+    auto* dst = (__attribute__((address_space(3))) char*)(ring + is_slot + wave * PPW * FRAG_BYTES);
     const int pi = is_i / SPP, j = is_i - pi * SPP;
     int pr = rot + pi;
     pr = pr % NP;                                   // issues run past the end: the stream wraps
-    const int src = (pr * SPP + j) * SG_SLAB;
+    const int src = (pr * SPP + j) * SLAB_BYTES;
     ++is_i;
-    sg_unroll([&](auto jc) {
+    unroll([&](auto jc) {
       constexpr int q = decltype(jc)::value;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, dst + q * SG_FRAG, 16, voff, src + (wave * PPW + q) * SG_FRAG, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, dst + q * FRAG_BYTES, 16, voff, src + (wave * PPW + q) * FRAG_BYTES, 0, 0);
     }, std::make_integer_sequence<int, PPW>{});
-    is_slot = is_slot + SG_SLAB == RING ? 0 : is_slot + SG_SLAB;
+    is_slot = is_slot + SLAB_BYTES == RING ? 0 : is_slot + SLAB_BYTES;
   };
 #pragma unroll
   for (int g = 0; g < SG_NSLOT - 1; ++g) issue_next();
@@ -182,9 +150,9 @@ void sg_kernel(SgArgs p) {
   int rd_slot = 0;
   auto rdA = [&](auto j_tag, auto fi_tag) -> u32x4 {
     constexpr int j = decltype(j_tag)::value, fi = decltype(fi_tag)::value;
-    int so = rd_slot + j * SG_SLAB;
+    int so = rd_slot + j * SLAB_BYTES;
     so = so >= RING ? so - RING : so;
-    return *reinterpret_cast<const u32x4*>(ring + so + lane * 16 + fi * SG_FRAG);
+    return *reinterpret_cast<const u32x4*>(ring + so + lane * 16 + fi * FRAG_BYTES);
   };
   auto sync = [&]() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW * (SG_NSLOT - 3)) : "memory");
@@ -192,11 +160,11 @@ void sg_kernel(SgArgs p) {
     issue_next();                                    // into the slot of the slab two behind
   };
   u32x4 a[SG_PF];
-  sg_unroll([&](auto ic) { a[decltype(ic)::value] = rdA(std::integral_constant<int, 0>{}, ic); },
+  unroll([&](auto ic) { a[decltype(ic)::value] = rdA(std::integral_constant<int, 0>{}, ic); },
             std::make_integer_sequence<int, SG_PF>{});
   // consume one tile pair (FPP fragments, whole slabs): mma(f, A) per fragment, LDS reads PF ahead
   auto run = [&](auto&& mma) {
-    sg_unroll([&](auto fc) {
+    unroll([&](auto fc) {
       constexpr int f = decltype(fc)::value;
       const u32x4 cur = a[f % SG_PF];
       if constexpr ((f & 15) == 16 - SG_PF) {
@@ -209,10 +177,10 @@ void sg_kernel(SgArgs p) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
     }, std::make_integer_sequence<int, FPP>{});
-    rd_slot += SPP * SG_SLAB;
+    rd_slot += SPP * SLAB_BYTES;
     rd_slot = rd_slot >= RING ? rd_slot - RING : rd_slot;
   };
-  const uint32_t sv_lane = sg_lds(sv) + 64 * hh;    // &sv[16 hh]
+  const uint32_t sv_lane = lds_byte_addr(sv) + 64 * hh;    // &sv[16 hh]
   // the pair's epilogue vectors (bias, rank columns, head weights) for this lane's features,
   // read in blocks of 8 with one wait each — NOT one wait per 4 features in the MFMA stream
   // b = bias + r1 c1 + r2 c2 (r1, r2: this lane's row scalars, so the rank terms fold into the
@@ -252,12 +220,12 @@ void sg_kernel(SgArgs p) {
     // ---- N = D: every tile kept (v = act(.) + x), then the row LayerNorm
     f32x16 acc[NT];
     float sum = 0.f, sq = 0.f;
-    sg_unroll([&](auto pc) {
+    unroll([&](auto pc) {
       constexpr int P = decltype(pc)::value;
       run([&](auto fc, const u32x4& A) {
         constexpr int f = decltype(fc)::value, T = 2 * P + f / KS, s = f % KS;
-        if constexpr (s == 0) acc[T] = sg_mfma(A, xa[0], f32x16{});
-        else acc[T] = sg_mfma(A, xa[s], acc[T]);
+        if constexpr (s == 0) acc[T] = mfma32(A, xa[0], f32x16{});
+        else acc[T] = mfma32(A, xa[s], acc[T]);
       });
     }, std::make_integer_sequence<int, NT / 2>{});
     PairVec pv;
@@ -272,7 +240,7 @@ void sg_kernel(SgArgs p) {
         for (int e = 0; e < 4; ++e) {
           const int i = 4 * q + e;                   // feature 32T + 16hh + i = x's k-step 2T + i/8, j = i%8
           const uint32_t w = xa[2 * T + (i >> 3)][(i & 7) >> 1];
-          const float v = y[e] + ((i & 1) ? __uint_as_float(w & 0xffff0000u) : __uint_as_float(w << 16));
+          const float v = y[e] + ((i & 1) ? bf_hi(w) : bf_lo(w));
           acc[T][i] = v;
           sum += v;
           sq = fmaf(v, v, sq);
@@ -302,8 +270,8 @@ void sg_kernel(SgArgs p) {
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2)
           *reinterpret_cast<u32x4*>(p.out + row * D + 32 * T + 16 * hh + 8 * h2) =
-              u32x4{sg_pack2(y[8 * h2], y[8 * h2 + 1]), sg_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                    sg_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), sg_pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
+              u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                    pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
       }
     }
     return;
@@ -323,8 +291,8 @@ void sg_kernel(SgArgs p) {
       float y[4];
       pre(acc[t], pv, t, q, y);
       if constexpr (EPI == SG_ACT) {
-        yo[2 * (q & 1)] = sg_pack2(y[0], y[1]);
-        yo[2 * (q & 1) + 1] = sg_pack2(y[2], y[3]);
+        yo[2 * (q & 1)] = pack2(y[0], y[1]);
+        yo[2 * (q & 1) + 1] = pack2(y[2], y[3]);
         if (q & 1) __builtin_amdgcn_raw_buffer_store_b128(yo, ors, row_off + 2 * (fb - 4), 0, 0);
       } else {
 #pragma unroll
@@ -341,8 +309,8 @@ void sg_kernel(SgArgs p) {
       if constexpr (PREV) load_vec(pp_prev, pv);
       run([&](auto fc, const u32x4& A) {
         constexpr int f = decltype(fc)::value, t = f / KS, s = f % KS;
-        if constexpr (s == 0) an[t] = sg_mfma(A, xa[0], f32x16{});
-        else an[t] = sg_mfma(A, xa[s], an[t]);
+        if constexpr (s == 0) an[t] = mfma32(A, xa[0], f32x16{});
+        else an[t] = mfma32(A, xa[s], an[t]);
         if constexpr (PREV && f % EVERY == 0) epi_step(ap, pp_prev, f / EVERY);
       });
     };
@@ -403,7 +371,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   constexpr int KS = D / 16, NT = D / 32, F1 = 2 * KS, F2 = 4 * NT, FPP = F1 + F2;
   static_assert(F1 % 16 == 0 && F2 % 16 == 0, "parts are whole slabs");
   constexpr int SPP = FPP / 16;
-  constexpr int RING = SG_NSLOT * SG_SLAB;
+  constexpr int RING = SG_NSLOT * SLAB_BYTES;
   constexpr int H = 4 * D, NP = H / 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem;
@@ -413,12 +381,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int ln = lane & 31, hh = lane >> 5;
   const long row = (long)blockIdx.x * 128 + wave * 32 + ln;
   const long rc = row < p.M ? row : (long)p.M - 1;
-  // first-round stagger (sg_kernel's): later rounds' activation loads and stores spread out
-  if (p.desync > 0 && blockIdx.x < 256) {
-    const long wait = (long)p.desync * ((blockIdx.x >> 3) & 7);
-    const long t0 = (long)__builtin_amdgcn_s_memtime();
-    while ((long)__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(16);
-  }
+  if (p.desync > 0 && blockIdx.x < 256) stagger_wait(p.desync);   // first-round stagger (mfma32.h)
   // vector table [b1 H | RANK: c1 H, c2 H | b2 D | LN: g D, be D]
   constexpr int OB2 = H * (RANK ? 3 : 1);
   const int nvec = OB2 + D * (EPI2 == 1 ? 3 : 1) + (AFG ? AFG_TAB : 0);
@@ -448,9 +411,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           const int u = 16 * hh + 8 * s + 2 * e + t;
           h[t] = gelu_erf(g1w[u * 2] * a0 + g1w[u * 2 + 1] * a1 + g1b[u]);
         }
-        const uint32_t w = sg_pack2(h[0], h[1]);
+        const uint32_t w = pack2(h[0], h[1]);
         hb[s][e] = w;
-        hl[s][e] = sg_pack2(h[0] - __uint_as_float(w << 16), h[1] - __uint_as_float(w & 0xffff0000u));
+        hl[s][e] = pack2(h[0] - bf_lo(w), h[1] - bf_hi(w));
       }
     // W2 fragments (tile T, step s, hi / lo) of the gate GEMV: afgate pack order, 1 KiB each
     const u32x4* gw = reinterpret_cast<const u32x4*>(p.g2) + lane;
@@ -462,12 +425,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int pt = 0; pt < 2; ++pt) w[s][pt] = gw[((T * 2 + s) * 2 + pt) * 64];
-      f32x16 g = sg_mfma(w[0][0], hb[0], f32x16{});
-      g = sg_mfma(w[0][0], hl[0], g);
-      g = sg_mfma(w[0][1], hb[0], g);
-      g = sg_mfma(w[1][0], hb[1], g);
-      g = sg_mfma(w[1][0], hl[1], g);
-      g = sg_mfma(w[1][1], hb[1], g);
+      f32x16 g = mfma32(w[0][0], hb[0], f32x16{});
+      g = mfma32(w[0][0], hl[0], g);
+      g = mfma32(w[0][1], hb[0], g);
+      g = mfma32(w[1][0], hb[1], g);
+      g = mfma32(w[1][0], hl[1], g);
+      g = mfma32(w[1][1], hb[1], g);
       float v[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) {                 // feature 32 T + 16 hh + i
@@ -479,13 +442,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        xa[2 * T][k] = sg_pack2(v[2 * k], v[2 * k + 1]);
-        xa[2 * T + 1][k] = sg_pack2(v[8 + 2 * k], v[9 + 2 * k]);
+        xa[2 * T][k] = pack2(v[2 * k], v[2 * k + 1]);
+        xa[2 * T + 1][k] = pack2(v[8 + 2 * k], v[9 + 2 * k]);
       }
     }
   } else {
 #pragma unroll
-    for (int s = 0; s < KS; ++s) xa[s] = *reinterpret_cast<const u32x4*>(p.x + rc * D + sg_in_feat(s, hh, 0));
+    for (int s = 0; s < KS; ++s) xa[s] = *reinterpret_cast<const u32x4*>(p.x + rc * D + in_feat(s, hh, 0));
   }
   float r1v = 0.f, r2v = 0.f;
   if constexpr (RANK) {
@@ -496,7 +459,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
   const int rot = (int)(blockIdx.x % NP);
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, NP * SPP * SG_SLAB, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, NP * SPP * SLAB_BYTES, 0x00020000);
   const int voff = lane * 16;
   int is_slot = 0, is_i = 0;
   // consumption order of the stream's blocks B(2P) = W1(P), B(2P + 1) = W2(P) (HS slabs each):
@@ -505,17 +468,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   constexpr int HS = F1 / 16;
   static_assert(F1 == F2, "equal W1 / W2 blocks per pair");
   auto issue_next = [&]() {
-    auto* dst = (__attribute__((address_space(3))) char*)(ring + is_slot + wave * 4 * SG_FRAG);
+    auto* dst = (__attribute__((address_space(3))) char*)(ring + is_slot + wave * 4 * FRAG_BYTES);
     const int b = is_i / HS, j = is_i - b * HS;
     int m = 2 * rot + b + ((b == 0 || b == 2 * NP - 1) ? 0 : (b & 1) ? 1 : -1);
     m %= 2 * NP;                                     // (issues past the end wrap: addresses stay valid)
-    const int src = (m * HS + j) * SG_SLAB;
+    const int src = (m * HS + j) * SLAB_BYTES;
     ++is_i;
-    sg_unroll([&](auto jc) {
+    unroll([&](auto jc) {
       constexpr int q = decltype(jc)::value;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, dst + q * SG_FRAG, 16, voff, src + (wave * 4 + q) * SG_FRAG, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, dst + q * FRAG_BYTES, 16, voff, src + (wave * 4 + q) * FRAG_BYTES, 0, 0);
     }, std::make_integer_sequence<int, 4>{});
-    is_slot = is_slot + SG_SLAB == RING ? 0 : is_slot + SG_SLAB;
+    is_slot = is_slot + SLAB_BYTES == RING ? 0 : is_slot + SLAB_BYTES;
   };
 #pragma unroll
   for (int g = 0; g < SG_NSLOT - 1; ++g) issue_next();
@@ -525,9 +488,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int rd_slot = 0;
   auto rdA = [&](auto j_tag, auto fi_tag) -> u32x4 {
     constexpr int j = decltype(j_tag)::value, fi = decltype(fi_tag)::value;
-    int so = rd_slot + j * SG_SLAB;
+    int so = rd_slot + j * SLAB_BYTES;
     so = so >= RING ? so - RING : so;
-    return *reinterpret_cast<const u32x4*>(ring + so + lane * 16 + fi * SG_FRAG);
+    return *reinterpret_cast<const u32x4*>(ring + so + lane * 16 + fi * FRAG_BYTES);
   };
   auto sync = [&]() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (SG_NSLOT - 3)) : "memory");
@@ -535,11 +498,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     issue_next();
   };
   u32x4 a[SG_PF];
-  sg_unroll([&](auto ic) { a[decltype(ic)::value] = rdA(std::integral_constant<int, 0>{}, ic); },
+  unroll([&](auto ic) { a[decltype(ic)::value] = rdA(std::integral_constant<int, 0>{}, ic); },
             std::make_integer_sequence<int, SG_PF>{});
   auto run = [&](auto nf_tag, auto&& mma) {
     constexpr int NF = decltype(nf_tag)::value;
-    sg_unroll([&](auto fc) {
+    unroll([&](auto fc) {
       constexpr int f = decltype(fc)::value;
       const u32x4 cur = a[f % SG_PF];
       if constexpr ((f & 15) == 16 - SG_PF) {
@@ -552,10 +515,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
     }, std::make_integer_sequence<int, NF>{});
-    rd_slot += (NF / 16) * SG_SLAB;
+    rd_slot += (NF / 16) * SLAB_BYTES;
     rd_slot = rd_slot >= RING ? rd_slot - RING : rd_slot;
   };
-  const uint32_t sv_lane = sg_lds(sv) + 64 * hh;
+  const uint32_t sv_lane = lds_byte_addr(sv) + 64 * hh;
   u32x4 pb[8];                                       // the pair's b1 (+ rank) for this lane's 32 units
   auto load_b1 = [&](int pp) {
     const uint32_t ad = sv_lane + 4 * 64 * pp;
@@ -581,16 +544,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     float y[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) y[j] = gelu_bf16(e[t][4 * q + j] + __uint_as_float(pb[k][j]));
-    hf[2 * t + (q >> 1)][2 * (q & 1)] = sg_pack2(y[0], y[1]);
-    hf[2 * t + (q >> 1)][2 * (q & 1) + 1] = sg_pack2(y[2], y[3]);
+    hf[2 * t + (q >> 1)][2 * (q & 1)] = pack2(y[0], y[1]);
+    hf[2 * t + (q >> 1)][2 * (q & 1) + 1] = pack2(y[2], y[3]);
   };
   constexpr int EVERY = F1 / 8;
   auto phase1 = [&](f32x16 (&en)[2], const f32x16 (&ep)[2], auto prev_tag) {
     constexpr bool PREV = decltype(prev_tag)::value;
     run(std::integral_constant<int, F1>{}, [&](auto fc, const u32x4& A) {
       constexpr int f = decltype(fc)::value, t = f / KS, s = f % KS;
-      if constexpr (s == 0) en[t] = sg_mfma(A, xa[0], f32x16{});
-      else en[t] = sg_mfma(A, xa[s], en[t]);
+      if constexpr (s == 0) en[t] = mfma32(A, xa[0], f32x16{});
+      else en[t] = mfma32(A, xa[s], en[t]);
       if constexpr (PREV && f % EVERY == 0) epi_step(ep, f / EVERY);
     });
   };
@@ -599,8 +562,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr bool FIRST = decltype(first_tag)::value;
     run(std::integral_constant<int, F2>{}, [&](auto fc, const u32x4& A) {
       constexpr int f = decltype(fc)::value;
-      if constexpr (FIRST && f < NT) acc[f] = sg_mfma(A, hf[0], f32x16{});
-      else acc[f % NT] = sg_mfma(A, hf[f / NT], acc[f % NT]);
+      if constexpr (FIRST && f < NT) acc[f] = mfma32(A, hf[0], f32x16{});
+      else acc[f % NT] = mfma32(A, hf[f / NT], acc[f % NT]);
     });
   };
   f32x16 e0[2], e1[2];
@@ -668,15 +631,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2)
         *reinterpret_cast<u32x4*>(p.out + row * D + 32 * T + 16 * hh + 8 * h2) =
-            u32x4{sg_pack2(y[8 * h2], y[8 * h2 + 1]), sg_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                  sg_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), sg_pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
+            u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                  pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
     }
   }
 }
 
 // MLP stream: per hidden pair P: W1 rows 64P .. 64P + 63 as in sg_pack (F = t KS + s), then
 // W2's 64 columns of the pair: fragment F2 = q NT + T, lane (m, kh) holds
-// W2[32T + sg_out_feat(m)][64P + sg_in_feat(q, kh, 0 .. 7)].
+// W2[32T + out_feat(m)][64P + in_feat(q, kh, 0 .. 7)].
 __global__ void mlp_pack_kernel(int D, long n_pieces, const bf16* __restrict__ w1, const bf16* __restrict__ w2,
                                 bf16* __restrict__ out) {
   const long pc = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -686,14 +649,13 @@ __global__ void mlp_pack_kernel(int D, long n_pieces, const bf16* __restrict__ w
   const int l = (int)(pc % 64), m = l & 31, kh = l >> 5;
   const long P = F / FPP;
   const int f = (int)(F % FPP);
-  if (f < F1) {
-    const int t = f / KS, s = f % KS;
-    const long n = 64 * P + 32 * t + sg_out_feat(m);
-    for (int j = 0; j < 8; ++j) out[pc * 8 + j] = w1[n * D + sg_in_feat(s, kh, j)];
+  if (f < F1) {                                      // fragment P F1 + f of W1's sg_pack stream
+    const PieceSrc q = sgemm_piece_src(D, (P * F1 + f) * 64 + l);
+    for (int j = 0; j < 8; ++j) out[pc * 8 + j] = w1[q.row * D + q.col + j];
   } else {
     const int f2 = f - F1, q = f2 / NT, T = f2 % NT;
-    const long n = 32 * T + sg_out_feat(m);
-    for (int j = 0; j < 8; ++j) out[pc * 8 + j] = w2[n * 4 * D + 64 * P + sg_in_feat(q, kh, j)];
+    const long n = 32 * T + out_feat(m);
+    for (int j = 0; j < 8; ++j) out[pc * 8 + j] = w2[n * 4 * D + 64 * P + in_feat(q, kh, j)];
   }
 }
 
@@ -703,27 +665,20 @@ static int mlp_launch(SgArgs a, hipStream_t s) {
   // first-round stagger (r6, tools/sg4_desync_sweep.py OPT=mlp_desync at the bench shapes): the
   // AF-gate form, whose prologue computes its input, 25 k cycles (0.83 vs 0.89 ms); the others 5 k
   // (af_fusion: 1.465 vs 1.489 ms)
-  const int64_t dz = options().mlp_desync;
-  a.desync = cdiv(a.M, 128) >= 4 * 256 ? (dz >= 0 ? (int)dz : (AFG ? 25000 : 5000)) : 0;
-  const size_t lds = (size_t)SG_NSLOT * SG_SLAB + SG_VEC_BYTES;
+  a.desync = stagger_step(cdiv(a.M, 128), 4 * 256, options().mlp_desync, AFG ? 25000 : 5000);
+  const size_t lds = (size_t)SG_NSLOT * SLAB_BYTES + SG_VEC_BYTES;
   SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, 128)), dim3(256), lds, s, a);
   SNV_LAUNCH_CHECK();
   return 0;
 }
 
-// One thread per 16-byte piece (8 bf16) of the stream: fragment F = T KS + s (output tile T, k-step
-// s), lane l = (m = l % 32, kh = l / 32) holds W[32T + sg_out_feat(m)][sg_in_feat(s, kh, 0 .. 7)].
+// One thread per 16-byte piece (8 bf16) of the stream, in sgemm_piece_src's order (mfma32.h)
 __global__ void sg_pack_kernel(int D, long n_pieces, const bf16* __restrict__ w, bf16* __restrict__ out) {
   const long pc = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (pc >= n_pieces) return;
-  const int KS = D / 16;
-  const long F = pc / 64;
-  const int l = (int)(pc % 64), m = l & 31, kh = l >> 5;
-  const long T = F / KS;
-  const int s = (int)(F % KS);
-  const long n = 32 * T + sg_out_feat(m);
-  for (int j = 0; j < 8; ++j) out[pc * 8 + j] = w[n * D + sg_in_feat(s, kh, j)];
+  const PieceSrc q = sgemm_piece_src(D, pc);
+  for (int j = 0; j < 8; ++j) out[pc * 8 + j] = w[q.row * D + q.col + j];
 }
 
 // snvrag_derive (see the header): one thread per 8 output elements; its job by binary search
@@ -745,28 +700,11 @@ __global__ __launch_bounds__(256) void derive_kernel(const snvrag_derive_job_t* 
     while (i < J.nparts - 1 && r >= J.part_rows[i]) { r -= J.part_rows[i]; ++i; }
     return J.src[i][r * J.rs[i] + c * J.cs[i]];
   };
-  if (J.kind == 2) {                                  // stream-GEMM pack (sg_pack_kernel's order)
-    const int D = (int)J.cols, KS = D / 16;
-    const long F = p / 64;
-    const int l = (int)(p % 64), m = l & 31, kh = l >> 5;
-    const long T = F / KS;
-    const int sidx = (int)(F % KS);
-    const long n = 32 * T + sg_out_feat(m);
+  if (J.kind == 2 || J.kind == 3) {                   // the stream-GEMM / wide-row GEMM pack of [rows, cols]
+    const PieceSrc q = J.kind == 2 ? sgemm_piece_src((int)J.cols, p) : gemm256_piece_src((int)(J.rows / 32), p);
     bf16x8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (bf16)src(n, sg_in_feat(sidx, kh, j));
-    *reinterpret_cast<bf16x8*>((bf16*)J.dst + p * 8) = o;
-    return;
-  }
-  if (J.kind == 3) {                                  // wide-row GEMM pack (gemm256.hip g2_pack_kernel's order)
-    const int NT = (int)(J.rows / 32);
-    const long F = p / 64;
-    const int l = (int)(p % 64), m = l & 31, kh = l >> 5;
-    const long k16 = F / NT;
-    const long n = 32 * (F % NT) + sg_out_feat(m);
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (bf16)src(n, 16 * k16 + 8 * kh + j);
+    for (int j = 0; j < 8; ++j) o[j] = (bf16)src(q.row, q.col + j);
     *reinterpret_cast<bf16x8*>((bf16*)J.dst + p * 8) = o;
     return;
   }
@@ -784,17 +722,16 @@ __global__ __launch_bounds__(256) void derive_kernel(const snvrag_derive_job_t* 
 template <int D, int EPI, int ACT, bool RANK, int WAVES = 4, bool CAT = false>
 static int sg_launch(SgArgs a, hipStream_t s) {
   auto kern = sg_kernel<D, EPI, ACT, RANK, WAVES, CAT>;
-  // first-round phase step (tail.hip's de-synchronised rounds): 10 k cycles for the 8-wave
+  // first-round phase step (stagger_wait, mfma32.h): 10 k cycles for the 8-wave
   // projections (QKV at M = 527 360: 0.559 -> 0.540 ms; 20 k / 30 k: 0.557 / 0.584,
   // tools/proj_micro.py); SNVRAG_SG_DESYNC overrides
   // 4-wave launches (r6, tools/sg4_desync_sweep.py): the LayerNorm form (emb_fusion: whole-tile
   // prologue and epilogue bursts) 5.5 k — 0.675 vs 0.772 ms; the others 10 k (cat GEMM 1.626 vs
   // 1.638, head 0.916 vs 0.920)
-  const int64_t dz = options().sg_desync;
-  a.desync = cdiv(a.M, 32 * WAVES) >= 4 * 256
-                 ? (dz >= 0 ? (int)dz : (WAVES == 8 ? 10000 : EPI == SG_LN ? 5500 : 10000)) : 0;
-  const size_t lds = (size_t)SG_NSLOT * SG_SLAB + SG_VEC_BYTES;
-  static_assert((size_t)SG_NSLOT * SG_SLAB + SG_VEC_BYTES <= 160 * 1024, "LDS budget");
+  a.desync = stagger_step(cdiv(a.M, 32 * WAVES), 4 * 256, options().sg_desync,
+                          WAVES == 8 ? 10000 : EPI == SG_LN ? 5500 : 10000);
+  const size_t lds = (size_t)SG_NSLOT * SLAB_BYTES + SG_VEC_BYTES;
+  static_assert((size_t)SG_NSLOT * SLAB_BYTES + SG_VEC_BYTES <= 160 * 1024, "LDS budget");
   SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, 32 * WAVES)), dim3(64 * WAVES), lds, s, a);
   SNV_LAUNCH_CHECK();

@@ -18,18 +18,15 @@
 //   * the FFN LayerNorm is folded: W2' = W2 diag(g_f), c1 = rowsum W2',
 //     b2' = b2 + W2 b_f, LN_f(h) W2^T + b2 = rstd (h W2'^T) - rstd mean c1 + b2'.
 // Lane (token n = lane % 32, half hh = lane / 32) holds output features 32T + 16hh + i
-// (i < 16) of tile T: weight ROWS are permuted at pack time (tail_out_feat), the input
-// feature order of every B fragment (tail_in_feat) is shared by W_o', W1 and the
+// (i < 16) of tile T: weight ROWS are permuted at pack time (out_feat), the input
+// feature order of every B fragment (in_feat) is shared by W_o', W1 and the
 // activation loads, so the LN epilogues, the x1 hand-over and the 32-B stores need no
 // lane exchange except one xor-32 shuffle per row reduction.
 #include "common.h"
-
-#include <utility>
+#include "mfma32.h"
 
 namespace snvrag {
 
-constexpr int TL_FRAG = 1024;               // one A fragment: 32 rows x 16 k bf16
-constexpr int TL_SLAB = 16 * TL_FRAG;
 constexpr int TL_NSLOT = 9;                 // ring slots (144 KiB)
 constexpr int TL_PF4 = 4;                   // A fragments read ahead: the template default and tail_variant 1
 constexpr int TL_PF_DEFAULT = 8;             // launch_tail's default (r3: 4: 1.634 ms, 8: 1.659 spilling; r5: 8 faster)
@@ -50,63 +47,9 @@ template <int D> struct TailShape {
   static_assert(FW1 % 16 == 0 && FW2 % 16 == 0 && FPRE % 16 == 0, "parts are whole slabs");
 };
 
-// output feature held by MFMA row m of 32-row tile T (lane half hh = (m/4)%2, acc i = 4(m/8) + m%4)
-__host__ __device__ constexpr int tail_out_feat(int T, int m) { return 32 * T + 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3); }
-// input feature at k = 8 kh + j of k-step s (B fragments of att / x1; columns of W_o', W1)
-__host__ __device__ constexpr int tail_in_feat(int s, int kh, int j) { return 32 * (s >> 1) + 16 * kh + 8 * (s & 1) + j; }
 // hidden unit (within a 64-unit chunk) at k = 8 kh + j of phase-2 k-step s2 (columns of W2')
 __host__ __device__ constexpr int tail_hid(int s2, int kh, int j) {
   return 32 * (s2 >> 1) + 8 * ((8 * (s2 & 1) + j) >> 2) + 4 * kh + ((8 * (s2 & 1) + j) & 3);
-}
-
-__device__ __forceinline__ f32x16 mfma32(const u32x4& a, const u32x4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-typedef __bf16 tl_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float tl_f32x2 __attribute__((ext_vector_type(2)));
-// two floats -> packed bf16 pair (RNE) in ONE v_cvt_pk_bf16_f32
-__device__ __forceinline__ uint32_t tl_pack2(float a, float b) {
-  const tl_f32x2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, tl_bf16x2));
-}
-// LeakyReLU(0.1) in 2 VALU ops (fmaxf on a register hipcc cannot prove canonical costs a third,
-// a v_max x, x canonicalisation)
-__device__ __forceinline__ float tl_lrelu(float x) {
-  float r;
-  asm("v_mul_f32 %0, 0x3dcccccd, %1\n v_max_f32 %0, %1, %0" : "=&v"(r) : "v"(x));
-  return r;
-}
-// 32-bit LDS address of a pointer into dynamic shared memory
-__device__ __forceinline__ uint32_t tl_lds(const char* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
-__device__ __forceinline__ float tl_lo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float tl_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ float tl_bf(const u32x4& v, int j) { return (j & 1) ? tl_hi(v[j >> 1]) : tl_lo(v[j >> 1]); }
-// lane id produced afresh at each use (volatile: not CSE'd with earlier ones), so no lane-derived
-// address stays live across the FFN and gets spilled
-__device__ __forceinline__ int tl_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-// x + x of the lane 32 apart (the row reductions over the two lane halves)
-__device__ __forceinline__ float tl_xsum32(float x) {
-  return x + __int_as_float(__builtin_amdgcn_ds_bpermute((tl_lane() ^ 32) << 2, __float_as_int(x)));
-}
-
-// 16 consecutive floats of an LDS table at byte address `addr` (this lane's features 16 hh .. +15
-// of a 32-feature tile): reads and their wait in ONE asm statement, so the compiler can neither
-// hoist them nor keep whole tables live in registers across a phase (tailp_kernel's epilogues)
-__device__ __forceinline__ void tl_ld16(uint32_t addr, float (&v)[16]) {
-  u32x4 r[4];
-  asm volatile(
-      "ds_read_b128 %0, %4 offset:0\n ds_read_b128 %1, %4 offset:16\n ds_read_b128 %2, %4 offset:32\n"
-      " ds_read_b128 %3, %4 offset:48\n s_waitcnt lgkmcnt(0)"
-      : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
-      : "v"(addr));
-#pragma unroll
-  for (int i = 0; i < 16; ++i) v[i] = __uint_as_float(r[i >> 2][i & 3]);
 }
 
 // wait until at most `younger` (<= MAXY) slabs of this wave (4 LDS-DMA instructions each) are in flight
@@ -123,13 +66,6 @@ template <int MAXY> __device__ __forceinline__ void tl_wait(int younger) {
   }
 }
 
-// calls body(std::integral_constant<int, I>{}) for I = 0 .. N-1: a forced full unroll (every
-// register-array index in the body is a compile-time constant)
-template <typename Body, int... Is>
-__device__ __forceinline__ void tl_unroll(Body&& body, std::integer_sequence<int, Is...>) {
-  (body(std::integral_constant<int, Is>{}), ...);
-}
-
 struct TailArgs {
   int M;
   const bf16* act;      // PRE: att [M, D]; else x1 [M, D]
@@ -140,7 +76,7 @@ struct TailArgs {
   const float* b_o; const float* g1; const float* be1;
   float eps;
   unsigned long long* stamps;   // VAR 2 (diagnostics): [workgroup][wave][TL_NSTAMP] s_memtime stamps
-  int desync;                   // > 0: first-round phase step in cycles (see tail_kernel)
+  int desync;                   // > 0: first-round phase step in cycles (stagger_wait, mfma32.h)
 };
 
 // diagnostic stamp points of VAR 2 (slot 0: s_memrealtime at entry, 1..: s_memtime)
@@ -163,7 +99,7 @@ void tail_kernel(TailArgs p) {
   constexpr bool PROJ = NC > 0;
   static_assert(!(PROJ && PRE), "modes");
   constexpr int NSLAB = (PRE ? S::NPRE : 0) + S::NCH * S::SPC;      // slabs consumed by this launch
-  constexpr int RING = TL_NSLOT * TL_SLAB;
+  constexpr int RING = TL_NSLOT * SLAB_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem;
   float* sv = reinterpret_cast<float*>(smem + RING);               // b1 [4D], g1, be1, b_o
@@ -183,23 +119,11 @@ void tail_kernel(TailArgs p) {
     }
   };
   stamp(TS_REAL0, true);
-  // De-synchronised rounds: every workgroup runs the same weight stream for the same time, so
-  // without this all 256 CUs start each round together and the prologue's activation + residual
-  // loads (192 KB per CU) and the epilogue's stores hit HBM as one chip-wide burst (measured:
-  // prologue 12 % of the wave, HBM-bound at ~4 TB/s, then idle HBM for the rest of the round).
-  // The first round's workgroups start at 8 phase offsets of `desync` cycles (per XCD: dispatch
-  // order blockIdx / 8), so later rounds stay spread and each CU's bursts overlap other CUs'
-  // MFMA phases.  The delay is paid once per CU; with >= 17 blocks per CU it ends inside the
-  // last partial round's slack.
-  if (p.desync > 0 && blockIdx.x < 256) {
-    const long wait = (long)p.desync * ((blockIdx.x >> 3) & 7);
-    const long t0 = (long)__builtin_amdgcn_s_memtime();
-    while ((long)__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(16);
-  }
+  if (p.desync > 0 && blockIdx.x < 256) stagger_wait(p.desync);   // de-synchronised rounds (mfma32.h)
   stamp(TS_START);
 
   // ---- vector tables to LDS first (their loads are waited on at once), then the activations
-  // as B fragments (k-step s: features tail_in_feat(s, hh, 0..7)); the residual rows of PRE are
+  // as B fragments (k-step s: features in_feat(s, hh, 0..7)); the residual rows of PRE are
   // loaded after the weight prologue (below) and only needed at LN1, so their HBM burst runs
   // under the out-projection MFMAs
   for (int i = tid; i < (PROJ ? NC : 4) * D; i += 256) sv[i] = p.vec[i];
@@ -210,7 +134,7 @@ void tail_kernel(TailArgs p) {
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     // (default cache policy: non-temporal activation loads/stores measured 8 % slower)
-    const u32x4 v = *reinterpret_cast<const u32x4*>(p.act + rc * D + tail_in_feat(s, hh, 0));
+    const u32x4 v = *reinterpret_cast<const u32x4*>(p.act + rc * D + in_feat(s, hh, 0));
     if constexpr (PRE || PROJ) xa[s] = v; else xr[s] = v;
   }
 
@@ -218,7 +142,7 @@ void tail_kernel(TailArgs p) {
   const int rot = (int)(blockIdx.x % (PROJ ? NC : S::NCH));
   constexpr int STREAM_SLABS = PROJ ? NC * S::NPRE : S::NSLAB;
   const __amdgpu_buffer_rsrc_t wrs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, STREAM_SLABS * TL_SLAB, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, STREAM_SLABS * SLAB_BYTES, 0x00020000);
   const int voff = lane * 16;
   // FFN block order (software pipeline, see the chunk loop): with the stream's blocks
   // B(2c) = W1(c), B(2c+1) = W2'(c) (H slabs each) and r = rot, block s of the launch is
@@ -234,7 +158,7 @@ void tail_kernel(TailArgs p) {
     if constexpr (PROJ) {                            // chunks rot, rot + 1, ... (mod NC), NPRE slabs each
       const int cc = i / S::NPRE, j = i - cc * S::NPRE;
       const int c = (rot + cc) % NC;
-      return (c * S::NPRE + j) * TL_SLAB;
+      return (c * S::NPRE + j) * SLAB_BYTES;
     }
     constexpr int NP = PRE ? S::NPRE : 0;
     const int q = i - NP > 0 ? i - NP : 0;
@@ -242,24 +166,24 @@ void tail_kernel(TailArgs p) {
     int m = 2 * rot + s + ((s == 0 || s == NB2 - 1) ? 0 : (s & 1) ? 1 : -1);
     m = m >= NB2 ? m - NB2 : m;
     m = m >= NB2 ? m - NB2 : m;                      // (overrun issues run past s = 2N - 1)
-    const int ffn = (S::NPRE + m * H + j) * TL_SLAB;
-    return i < NP ? i * TL_SLAB : ffn;
+    const int ffn = (S::NPRE + m * H + j) * SLAB_BYTES;
+    return i < NP ? i * SLAB_BYTES : ffn;
   };
   // Issues run NSLOT - 2 slabs past the end of the launch's stream (the wrapped stream
   // continues, so the addresses stay valid): every sync then has the same number of slabs in
   // flight behind the one it waits for — one constant vmcnt, no per-slab branches.  The
   // overrun lands in slots nobody reads; the epilogue drains it before reusing the ring.
   auto issue_next = [&]() {
-    auto* dst = (__attribute__((address_space(3))) void*)(ring + is_slot + wave * 4 * TL_FRAG);
+    auto* dst = (__attribute__((address_space(3))) void*)(ring + is_slot + wave * 4 * FRAG_BYTES);
     const int src = src_of(is_i);
     ++is_i;
-    tl_unroll([&](auto jc) {
+    unroll([&](auto jc) {
       constexpr int j = decltype(jc)::value;
       // (instruction offset 0: the slab offset rides in soffset, the LDS slot in M0)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) char*)dst + j * TL_FRAG, 16,
-                                               voff, src + (wave * 4 + j) * TL_FRAG, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) char*)dst + j * FRAG_BYTES, 16,
+                                               voff, src + (wave * 4 + j) * FRAG_BYTES, 0, 0);
     }, std::make_integer_sequence<int, 4>{});
-    is_slot = is_slot + TL_SLAB == RING ? 0 : is_slot + TL_SLAB;
+    is_slot = is_slot + SLAB_BYTES == RING ? 0 : is_slot + SLAB_BYTES;
   };
 #pragma unroll
   for (int g = 0; g < TL_NSLOT - 1; ++g) issue_next();
@@ -282,9 +206,9 @@ void tail_kernel(TailArgs p) {
   int rd_slot = 0;
   auto rdA = [&](auto j_tag, auto fi_tag) -> u32x4 {   // fragment fi of the part's slab j
     constexpr int j = decltype(j_tag)::value, fi = decltype(fi_tag)::value;
-    int so = rd_slot + j * TL_SLAB;
+    int so = rd_slot + j * SLAB_BYTES;
     so = so >= RING ? so - RING : so;
-    return *reinterpret_cast<const u32x4*>(ring + so + lane * 16 + fi * TL_FRAG);
+    return *reinterpret_cast<const u32x4*>(ring + so + lane * 16 + fi * FRAG_BYTES);
   };
   // sync before the first read of slab g (reached PF fragments before its boundary)
   // (g is a compile-time constant where it matters: PRE's first NSLOT - 2 slabs, issued before
@@ -314,7 +238,7 @@ void tail_kernel(TailArgs p) {
     constexpr int G0 = decltype(g0_tag)::value;
     constexpr bool STOP = decltype(stop_tag)::value;
     static_assert(NF % 16 == 0, "parts are whole slabs");
-    tl_unroll([&](auto fc) {
+    unroll([&](auto fc) {
       constexpr int f = decltype(fc)::value;
       const u32x4 cur = a[f % TL_PF];
       if constexpr ((f & 15) == 16 - TL_PF) {
@@ -334,11 +258,11 @@ void tail_kernel(TailArgs p) {
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
     }, std::make_integer_sequence<int, NF>{});
-    rd_slot += (NF / 16) * TL_SLAB;
+    rd_slot += (NF / 16) * SLAB_BYTES;
     rd_slot = rd_slot >= RING ? rd_slot - RING : rd_slot;
   };
   auto prime = [&]() {
-    tl_unroll([&](auto ic) { a[decltype(ic)::value] = rdA(std::integral_constant<int, 0>{}, ic); },
+    unroll([&](auto ic) { a[decltype(ic)::value] = rdA(std::integral_constant<int, 0>{}, ic); },
               std::make_integer_sequence<int, TL_PF>{});
   };
 
@@ -351,7 +275,7 @@ void tail_kernel(TailArgs p) {
     // The NT x 2 stores of chunk c go out PPS per slab during chunk c + 1's stream (bounds-
     // checked buffer stores: rows >= M fall outside the resource and are dropped): a burst of
     // stores right before a sync would hold that sync's vmcnt wait until they completed.
-    const uint32_t sv_lane = tl_lds(reinterpret_cast<const char*>(sv)) + 64 * hh;   // &sv[16 hh]
+    const uint32_t sv_lane = lds_byte_addr(sv) + 64 * hh;   // &sv[16 hh]
     const long out_bytes = (long)p.M * NC * D * 2;
     const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
         (void*)p.out, (short)0, (int)(out_bytes < 0x7fffffffL ? out_bytes : 0x7fffffffL), 0x00020000);
@@ -368,7 +292,7 @@ void tail_kernel(TailArgs p) {
     };
     auto chunk = [&](int c, auto stores_tag) {
       constexpr bool STORES = decltype(stores_tag)::value;
-      tl_unroll([&](auto gc) {
+      unroll([&](auto gc) {
         constexpr int g = decltype(gc)::value;
         run(std::integral_constant<int, 4 * NT>{}, std::integral_constant<int, -1>{}, [&](auto fc, const u32x4& A) {
           constexpr int f = decltype(fc)::value;
@@ -376,7 +300,7 @@ void tail_kernel(TailArgs p) {
           else acc[f % NT] = mfma32(A, xa[4 * g + f / NT], acc[f % NT]);
           if constexpr (STORES && (f & 15) == 16 - TL_PF) {
             constexpr int slab = g * (NT / 4) + (f >> 4);
-            tl_unroll([&](auto pc) { store_pair(std::integral_constant<int, slab * PPS + decltype(pc)::value>{}); },
+            unroll([&](auto pc) { store_pair(std::integral_constant<int, slab * PPS + decltype(pc)::value>{}); },
                       std::make_integer_sequence<int, PPS>{});
           }
         }, std::false_type{});
@@ -396,15 +320,15 @@ void tail_kernel(TailArgs p) {
         for (int i = 0; i < 16; ++i) y[i] = acc[T][i] + __uint_as_float(bv[i >> 2][i & 3]);
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2)
-          yo[2 * T + h2] = u32x4{tl_pack2(y[8 * h2], y[8 * h2 + 1]), tl_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                                 tl_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), tl_pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
+          yo[2 * T + h2] = u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                                 pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
       }
       yo_off = row_off + c * D * 2;
     };
     chunk(rot, std::false_type{});
 #pragma unroll 1
     for (int cc = 1; cc < NC; ++cc) chunk((rot + cc) % NC, std::true_type{});
-    tl_unroll([&](auto tc) { store_pair(tc); }, std::make_integer_sequence<int, NT>{});
+    unroll([&](auto tc) { store_pair(tc); }, std::make_integer_sequence<int, NT>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stream overrun has landed before exit
     return;
   }
@@ -424,13 +348,13 @@ void tail_kernel(TailArgs p) {
     // LN1's first pass (frees its registers before LN1, but waits for the residual burst earlier:
     // measured slower, tools/tail_micro.py)
     constexpr int RR_G = (VAR == 3 && KS / 4 > 3) ? 3 : -1;
-    tl_unroll([&](auto gc) {
+    unroll([&](auto gc) {
       constexpr int g = decltype(gc)::value;
       if constexpr (g == RR_G) {
 #pragma unroll
         for (int T = 0; T < NT; ++T)
 #pragma unroll
-          for (int i = 0; i < 16; ++i) ao[T][i] += tl_bf(rr[2 * T + (i >> 3)], i & 7);
+          for (int i = 0; i < 16; ++i) ao[T][i] += bf_at(rr[2 * T + (i >> 3)], i & 7);
       }
       run(std::integral_constant<int, 4 * NT>{}, std::integral_constant<int, g * (NT / 4)>{}, [&](auto fc, const u32x4& A) {
         constexpr int f = decltype(fc)::value;
@@ -447,7 +371,7 @@ void tail_kernel(TailArgs p) {
       for (int i = 0; i < 16; ++i) {
         float v = ao[T][i];
         if constexpr (RR_G < 0) {
-          v += tl_bf(rr[2 * T + (i >> 3)], i & 7);
+          v += bf_at(rr[2 * T + (i >> 3)], i & 7);
           ao[T][i] = v;
         }
         sum += v;
@@ -456,8 +380,8 @@ void tail_kernel(TailArgs p) {
 #pragma unroll
     for (int T = 0; T < NT; ++T) asm volatile("" : "+a"(ao[T]));
     asm volatile("" ::: "memory");
-    sum = tl_xsum32(sum);
-    sq = tl_xsum32(sq);
+    sum = xsum32(sum);
+    sq = xsum32(sq);
     const float mean = sum * (1.0f / D);
     const float rstd = 1.0f / sqrtf(fmaxf(sq * (1.0f / D) - mean * mean, 0.f) + p.eps);
 #pragma unroll
@@ -470,8 +394,8 @@ void tail_kernel(TailArgs p) {
       }
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2)
-        xr[2 * T + h2] = u32x4{tl_pack2(y[8 * h2], y[8 * h2 + 1]), tl_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                               tl_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), tl_pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
+        xr[2 * T + h2] = u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                               pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
     }
     // the FFN's first fragments are read only now: read ahead across LN1 they were live through
     // it and spilled, and their scratch reloads waited on vmcnt(0), i.e. drained the weight ring
@@ -488,17 +412,17 @@ void tail_kernel(TailArgs p) {
   // its hidden into phase-2 B fragments) is interleaved between them; then phase 2 (W2') of
   // chunk k-1.  Stream order: W1(0), W1(1), W2'(0), W1(2), W2'(1), ..., W2'(N-1).
   float st1 = 0.f, st2 = 0.f;
-  const uint32_t sv_lane = tl_lds(reinterpret_cast<const char*>(sv)) + 16 * hh;
+  const uint32_t sv_lane = lds_byte_addr(sv) + 16 * hh;
   f32x16 h0[2], h1[2];                               // hidden of even / odd chunks (ping-pong)
   u32x4 hf[4];                                       // phase-2 B fragments (k-step 2t + q)
   auto epi_pair = [&](const f32x16 (&hc)[2], int m) {   // hidden values 2m, 2m+1 of hc (m < 16)
     const int t = m >> 3, i = 2 * (m & 7);
     float x0 = hc[t][i], x1 = hc[t][i + 1];
-    x0 = tl_lrelu(x0);
-    x1 = tl_lrelu(x1);
+    x0 = lrelu(x0);
+    x1 = lrelu(x1);
     st1 += x0 + x1;
     st2 = fmaf(x0, x0, fmaf(x1, x1, st2));
-    hf[2 * t + (i >> 3)][(i & 7) >> 1] = tl_pack2(x0, x1);
+    hf[2 * t + (i >> 3)][(i & 7) >> 1] = pack2(x0, x1);
   };
   // phase 1 of chunk k into hn: h^T = W1_c x1^T + b1 (fragment f: k-step f / 2, tile f % 2; the
   // bias is the C operand of the first k-step, hidden unit of acc element i: 8(i/4) + 4hh + i%4),
@@ -562,14 +486,14 @@ void tail_kernel(TailArgs p) {
 
   stamp(TS_FFN);
   // ---- epilogue: out = LN2(x1 + lrelu(rstd_f acc - rstd_f mean_f c1 + b2'))
-  st1 = tl_xsum32(st1);
-  st2 = tl_xsum32(st2);
+  st1 = xsum32(st1);
+  st2 = xsum32(st2);
   const float hm = st1 * (1.0f / (4 * D));
   const float hr = 1.0f / sqrtf(fmaxf(st2 * (1.0f / (4 * D)) - hm * hm, 0.f) + p.eps);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the stream overrun has landed
   __syncthreads();                                   // every wave is done with the ring
   float* ev = reinterpret_cast<float*>(ring);        // [b2' | c1 | g2 | be2]
-  for (int i = wave * 64 + tl_lane(); i < 4 * D; i += 256) ev[i] = p.vec[4 * D + i];   // fresh tid (no spill)
+  for (int i = wave * 64 + lane_id(); i < 4 * D; i += 256) ev[i] = p.vec[4 * D + i];   // fresh tid (no spill)
   __syncthreads();
   stamp(TS_EPI);
   const float* b2 = ev;
@@ -585,8 +509,8 @@ void tail_kernel(TailArgs p) {
     for (int i = 0; i < 16; ++i) {
       const int ft = 32 * T + 16 * hh + i;
       float u = hr * fmaf(-hm, c1[ft], acc[T][i]) + b2[ft];
-      u = tl_lrelu(u);
-      const float v = u + tl_bf(xr[2 * T + (i >> 3)], i & 7);
+      u = lrelu(u);
+      const float v = u + bf_at(xr[2 * T + (i >> 3)], i & 7);
       acc[T][i] = v;
       sum += v;
       sq = fmaf(v, v, sq);
@@ -597,14 +521,14 @@ void tail_kernel(TailArgs p) {
 #pragma unroll
   for (int T = 0; T < NT; ++T) asm volatile("" : "+a"(acc[T]));
   asm volatile("" ::: "memory");
-  sum = tl_xsum32(sum);
-  sq = tl_xsum32(sq);
+  sum = xsum32(sum);
+  sq = xsum32(sq);
   const float mean = sum * (1.0f / D);
   const float rstd = 1.0f / sqrtf(fmaxf(sq * (1.0f / D) - mean * mean, 0.f) + p.eps);
   const float nmr = -mean * rstd;
   auto v2 = [&](int T, int i) { return fmaf(acc[T][i], rstd, nmr); };
   // the row recomputed from a fresh lane id (kept live from the prologue it was spilled)
-  const long row_e = (long)blockIdx.x * TL_ROWS + wave * 32 + (tl_lane() & 31);
+  const long row_e = (long)blockIdx.x * TL_ROWS + wave * 32 + (lane_id() & 31);
   if (row_e < p.M) {
 #pragma unroll
     for (int T = 0; T < NT; ++T) {
@@ -617,8 +541,8 @@ void tail_kernel(TailArgs p) {
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2)
         *reinterpret_cast<u32x4*>(p.out + row_e * D + 32 * T + 16 * hh + 8 * h2) =
-            u32x4{tl_pack2(y[8 * h2], y[8 * h2 + 1]), tl_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                  tl_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), tl_pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
+            u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                  pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
     }
   }
   if constexpr (VAR == 2) {
@@ -666,7 +590,7 @@ void tailp_kernel(TailArgs p) {
   static_assert(S::NPRE == NA * WPG, "W_o' groups");
   constexpr int NQ = Q_FFN + S::NCH * S::SPC;         // slabs per tile
   constexpr int AHEAD = TP_NSLOT - 2;                 // sync(g) issues slab g + AHEAD
-  constexpr int RING = TP_NSLOT * TL_SLAB;
+  constexpr int RING = TP_NSLOT * SLAB_BYTES;
   constexpr int VM = 4 * (TP_NSLOT - 3);              // vmcnt at a sync: the younger slabs in flight
   constexpr int NST = 2 * NT;                         // epilogue stores per lane and tile
   constexpr int H = S::FW1 / 16;                      // slabs per W1 / W2' block
@@ -698,11 +622,7 @@ void tailp_kernel(TailArgs p) {
   for (int i = tid; i < D; i += 256) { sv[8 * D + i] = p.g1[i]; sv[9 * D + i] = p.be1[i]; sv[10 * D + i] = p.b_o[i]; }
   // first-tile stagger (tail_kernel's desync), only for the workgroups with one tile fewer: their
   // slack absorbs it
-  if (p.desync > 0 && ntiles % G != 0 && (int)blockIdx.x >= ntiles % G && ntiles >= 8 * G) {
-    const long wait = (long)p.desync * ((blockIdx.x >> 3) & 7);
-    const long t0 = (long)__builtin_amdgcn_s_memtime();
-    while ((long)__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(16);
-  }
+  if (p.desync > 0 && ntiles % G != 0 && (int)blockIdx.x >= ntiles % G && ntiles >= 8 * G) stagger_wait(p.desync);
 
   // ---- issue side.  Every issue target is a compile-time tile-relative slab index (the loop's
   // are compile-time offsets from the iteration's runtime block base), so an issue is a few scalar
@@ -710,9 +630,9 @@ void tailp_kernel(TailArgs p) {
   // mod 2 NCH (tail_kernel's rotated order), the activation pieces through a resource starting at
   // the tile's rows (rows >= M, and tiles >= ntiles, read as zeros).
   const int rot2 = 2 * (int)(blockIdx.x % S::NCH);
-  const i32x4 wrs = dma_rsrc(p.ws, (long)S::NSLAB * TL_SLAB);
-  const uint32_t ring_lds = lds_addr(ring) + wave * 4 * TL_FRAG;
-  const int wave_off = wave * 4 * TL_FRAG;
+  const i32x4 wrs = dma_rsrc(p.ws, (long)S::NSLAB * SLAB_BYTES);
+  const uint32_t ring_lds = lds_addr(ring) + wave * 4 * FRAG_BYTES;
+  const int wave_off = wave * 4 * FRAG_BYTES;
   int is_slot = 0;                                    // ring slot (byte offset) of the next issue
   long tb = (long)blockIdx.x * TL_ROWS * D * 2;       // byte offset of the current tile's rows
   constexpr int TB_STEP = TL_ROWS * D * 2;
@@ -724,19 +644,19 @@ void tailp_kernel(TailArgs p) {
   // 16-B chunks XOR-swizzled by row & 7 (conflict-free fragment reads): lane l fills row
   // 8 j + l / 8, slot l % 8, so it loads chunk (l % 8) ^ (row % 8).  From a fresh lane id.
   auto voff_act = [&](int j) {
-    const int l = tl_lane();
+    const int l = lane_id();
     return (opq(wave) * 32 + 8 * j + (l >> 3)) * (D * 2) + 16 * ((l & 7) ^ ((l >> 3) & 7));
   };
   auto put = [&](const i32x4& rs, int soff, bool act) {
     const int lds = opq(ring_lds) + is_slot;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      dma_x4(rs, lds + j * TL_FRAG, act ? voff_act(j) : tl_lane() * 16, act ? soff : soff + j * TL_FRAG);
-    is_slot = is_slot + TL_SLAB == RING ? 0 : is_slot + TL_SLAB;
+      dma_x4(rs, lds + j * FRAG_BYTES, act ? voff_act(j) : lane_id() * 16, act ? soff : soff + j * FRAG_BYTES);
+    is_slot = is_slot + SLAB_BYTES == RING ? 0 : is_slot + SLAB_BYTES;
   };
   auto ffn_off = [&](int m) {                         // m in [0, 2 NB2)
     m = m >= NB2 ? m - NB2 : m;
-    return (S::NPRE * TL_SLAB) + m * (H * TL_SLAB);
+    return (S::NPRE * SLAB_BYTES) + m * (H * SLAB_BYTES);
   };
   // target QG: tile-relative slab (>= NQ: the next tile's); compile-time
   auto issue_ct = [&](auto q_tag) {
@@ -753,11 +673,11 @@ void tailp_kernel(TailArgs p) {
       const char* base = reinterpret_cast<const char*>(rq == 0 ? p.act : p.resid);
       put(dma_rsrc(base + (left > 0 ? tbl : 0), left > 0 ? left : 0), 128 * gq, true);
     } else if constexpr (q < Q_FFN) {
-      put(wrs, (gq * WPG + rq - 1) * TL_SLAB + opq(wave_off), false);
+      put(wrs, (gq * WPG + rq - 1) * SLAB_BYTES + opq(wave_off), false);
     } else {
       constexpr int qq = q - Q_FFN, sb = qq / H, jb = qq % H;
       constexpr int d = (sb == 0 || sb == NB2 - 1) ? 0 : (sb & 1) ? 1 : -1;
-      put(wrs, ffn_off(opq(rot2) + sb + d) + jb * TL_SLAB + opq(wave_off), false);
+      put(wrs, ffn_off(opq(rot2) + sb + d) + jb * SLAB_BYTES + opq(wave_off), false);
     }
   };
   // loop target: slab Q_LOOP + AHEAD + 4 H it + C; mloop = rot2 + 4 it (runtime)
@@ -766,12 +686,12 @@ void tailp_kernel(TailArgs p) {
     constexpr int qq = Q_LOOP + AHEAD - Q_FFN + C, sb = qq / H, jb = qq % H;   // block of iteration 0
     constexpr int d = (sb & 1) ? 1 : -1;
     static_assert(sb > 0 && sb + 4 * (LOOP_IT - 1) < NB2 - 1, "loop targets are plain blocks");
-    put(wrs, ffn_off(mloop + sb + d) + jb * TL_SLAB + opq(wave_off), false);
+    put(wrs, ffn_off(mloop + sb + d) + jb * SLAB_BYTES + opq(wave_off), false);
   };
   // the vector tables landed (plain loads), then the first AHEAD slabs
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
-  tl_unroll([&](auto gc) { issue_ct(gc); }, std::make_integer_sequence<int, AHEAD>{});
+  unroll([&](auto gc) { issue_ct(gc); }, std::make_integer_sequence<int, AHEAD>{});
 
   // sync before reading slab g: it has landed (this wave's pieces: vmcnt; the others': barrier)
   auto wait_bar = [&](auto vm_tag) {
@@ -796,19 +716,19 @@ void tailp_kernel(TailArgs p) {
   int rd_slot = 0;
   auto rdA = [&](auto j_tag, auto fi_tag) -> u32x4 {
     constexpr int j = decltype(j_tag)::value, fi = decltype(fi_tag)::value;
-    int so = rd_slot + j * TL_SLAB;
+    int so = rd_slot + j * SLAB_BYTES;
     so = so >= RING ? so - RING : so;
-    return *reinterpret_cast<const u32x4*>(ring + so + lane * 16 + fi * TL_FRAG);
+    return *reinterpret_cast<const u32x4*>(ring + so + lane * 16 + fi * FRAG_BYTES);
   };
   // B fragment j of this wave's rows in the current A / R slab (features 64 slab + 32 (j / 2) +
   // 16 hh + 8 (j % 2) .. + 7 of row ln: 16-B chunk 4 (j / 2) + 2 hh + j % 2 of the row's 128 B)
   auto rdOwn = [&](int j) -> u32x4 {
-    const int l = tl_lane(), ln = l & 31;
+    const int l = lane_id(), ln = l & 31;
     const int c = 4 * (j >> 1) + 2 * (l >> 5) + (j & 1);
     return *reinterpret_cast<const u32x4*>(ring + rd_slot + opq(wave_off) + ln * 128 + 16 * (c ^ (ln & 7)));
   };
   auto advance = [&](int n) {
-    rd_slot += n * TL_SLAB;
+    rd_slot += n * SLAB_BYTES;
     rd_slot = rd_slot >= RING ? rd_slot - RING : rd_slot;
   };
 
@@ -822,7 +742,7 @@ void tailp_kernel(TailArgs p) {
     constexpr int P = decltype(p_tag)::value;
     constexpr bool STOP = decltype(stop_tag)::value;
     static_assert(NF % 16 == 0, "parts are whole slabs");
-    tl_unroll([&](auto fc) {
+    unroll([&](auto fc) {
       constexpr int f = decltype(fc)::value;
       const u32x4 cur = a[f % PF];
       if constexpr ((f & 15) == 16 - PF) {
@@ -845,14 +765,14 @@ void tailp_kernel(TailArgs p) {
     advance(NF / 16);
   };
   auto prime = [&]() {
-    tl_unroll([&](auto ic) { a[decltype(ic)::value] = rdA(std::integral_constant<int, 0>{}, ic); },
+    unroll([&](auto ic) { a[decltype(ic)::value] = rdA(std::integral_constant<int, 0>{}, ic); },
               std::make_integer_sequence<int, PF>{});
   };
   using I0 = std::integral_constant<int, 0>;
 
   // table t, tile T: this lane's 16 floats (features 32 T + 16 hh + i)
   auto tab = [&](int t, int T, float (&v)[16]) {
-    tl_ld16(opq(tl_lds(reinterpret_cast<const char*>(sv))) + 4 * (t * D + 32 * T) + 64 * (tl_lane() >> 5), v);
+    ld16(opq(lds_byte_addr(sv)) + 4 * (t * D + 32 * T) + 64 * (lane_id() >> 5), v);
   };
   enum { TB_B2 = 4, TB_C1 = 5, TB_G2 = 6, TB_BE2 = 7, TB_G1 = 8, TB_BE1 = 9, TB_BO = 10 };
   const long out_bytes = (long)M * D * 2;
@@ -885,7 +805,7 @@ void tailp_kernel(TailArgs p) {
       for (int i = 0; i < 16; ++i) ao[T][i] = bo[i];
     }
     u32x4 rr[2 * NT];
-    tl_unroll([&](auto gc) {
+    unroll([&](auto gc) {
       constexpr int g = decltype(gc)::value;
       constexpr int QA = g * GS;
       if constexpr (g > 0) sync_ct(std::integral_constant<int, QA>{}, vm_of(std::integral_constant<int, QA>{}));
@@ -917,7 +837,7 @@ void tailp_kernel(TailArgs p) {
       for (int T = 0; T < NT; ++T)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const float v = ao[T][i] + tl_bf(rr[2 * T + (i >> 3)], i & 7);
+          const float v = ao[T][i] + bf_at(rr[2 * T + (i >> 3)], i & 7);
           ao[T][i] = v;
           sum += v;
           sq = fmaf(v, v, sq);
@@ -925,8 +845,8 @@ void tailp_kernel(TailArgs p) {
 #pragma unroll
       for (int T = 0; T < NT; ++T) asm volatile("" : "+a"(ao[T]));
       asm volatile("" ::: "memory");
-      sum = tl_xsum32(sum);
-      sq = tl_xsum32(sq);
+      sum = xsum32(sum);
+      sq = xsum32(sq);
       const float mean = sum * (1.0f / D);
       const float rstd = 1.0f / sqrtf(fmaxf(sq * (1.0f / D) - mean * mean, 0.f) + p.eps);
 #pragma unroll
@@ -938,8 +858,8 @@ void tailp_kernel(TailArgs p) {
         for (int i = 0; i < 16; ++i) y[i] = (ao[T][i] - mean) * rstd * g1v[i] + be1v[i];
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2)
-          xr[2 * T + h2] = u32x4{tl_pack2(y[8 * h2], y[8 * h2 + 1]), tl_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                                 tl_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), tl_pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
+          xr[2 * T + h2] = u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                                 pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
       }
     }
     prime();
@@ -955,11 +875,11 @@ void tailp_kernel(TailArgs p) {
     auto epi_pair = [&](const f32x16 (&hc)[2], int m) {
       const int tt = m >> 3, i = 2 * (m & 7);
       float x0 = hc[tt][i], x1 = hc[tt][i + 1];
-      x0 = tl_lrelu(x0);
-      x1 = tl_lrelu(x1);
+      x0 = lrelu(x0);
+      x1 = lrelu(x1);
       st1 += x0 + x1;
       st2 = fmaf(x0, x0, fmaf(x1, x1, st2));
-      hf[2 * tt + (i >> 3)][(i & 7) >> 1] = tl_pack2(x0, x1);
+      hf[2 * tt + (i >> 3)][(i & 7) >> 1] = pack2(x0, x1);
     };
     // G0: the part's first tile slab (compile-time) or < 0 for a loop part at block offset P
     auto phase1 = [&](int k, f32x16 (&hn)[2], const f32x16 (&hc)[2], auto epi_tag, auto g0_tag, auto p_tag,
@@ -967,7 +887,7 @@ void tailp_kernel(TailArgs p) {
       constexpr bool EPI = decltype(epi_tag)::value;
       int c = k + (int)((unsigned)opq(rot2) >> 1);
       c = c >= S::NCH ? c - S::NCH : c;
-      const uint32_t b1 = opq(tl_lds(reinterpret_cast<const char*>(sv))) + 16 * (tl_lane() >> 5) + 256 * c;
+      const uint32_t b1 = opq(lds_byte_addr(sv)) + 16 * (lane_id() >> 5) + 256 * c;
       u32x4 bv[8];
       asm volatile(
           "ds_read_b128 %0, %8 offset:0\n ds_read_b128 %1, %8 offset:32\n ds_read_b128 %2, %8 offset:64\n"
@@ -1022,7 +942,7 @@ void tailp_kernel(TailArgs p) {
     }
     // the remaining iterations, unrolled: compile-time issue targets (they reach W2'(N-1) and
     // the next tile)
-    tl_unroll([&](auto ic) {
+    unroll([&](auto ic) {
       constexpr int it = LOOP_IT + decltype(ic)::value;
       constexpr int kb = 5 + 4 * it;                      // its first block
       constexpr int k = 3 + 2 * it;
@@ -1041,8 +961,8 @@ void tailp_kernel(TailArgs p) {
 
     mark(5);
     // ---- epilogue: out = LN2(x1 + lrelu(rstd_f acc - rstd_f mean_f c1 + b2'))
-    st1 = tl_xsum32(st1);
-    st2 = tl_xsum32(st2);
+    st1 = xsum32(st1);
+    st2 = xsum32(st2);
     const float hm = st1 * (1.0f / (4 * D));
     const float hr = 1.0f / sqrtf(fmaxf(st2 * (1.0f / (4 * D)) - hm * hm, 0.f) + p.eps);
     float sum = 0.f, sq = 0.f;
@@ -1054,8 +974,8 @@ void tailp_kernel(TailArgs p) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         float u = hr * fmaf(-hm, c1v[i], acc[T][i]) + b2v[i];
-        u = tl_lrelu(u);
-        const float v = u + tl_bf(xr[2 * T + (i >> 3)], i & 7);
+        u = lrelu(u);
+        const float v = u + bf_at(xr[2 * T + (i >> 3)], i & 7);
         acc[T][i] = v;
         sum += v;
         sq = fmaf(v, v, sq);
@@ -1064,12 +984,12 @@ void tailp_kernel(TailArgs p) {
 #pragma unroll
     for (int T = 0; T < NT; ++T) asm volatile("" : "+a"(acc[T]));
     asm volatile("" ::: "memory");
-    sum = tl_xsum32(sum);
-    sq = tl_xsum32(sq);
+    sum = xsum32(sum);
+    sq = xsum32(sq);
     const float mean = sum * (1.0f / D);
     const float rstd = 1.0f / sqrtf(fmaxf(sq * (1.0f / D) - mean * mean, 0.f) + p.eps);
     const float nmr = -mean * rstd;
-    const int row_off = (int)(((long)t * TL_ROWS + wave * 32 + (tl_lane() & 31)) * D + 16 * (tl_lane() >> 5)) * 2;
+    const int row_off = (int)(((long)t * TL_ROWS + wave * 32 + (lane_id() & 31)) * D + 16 * (lane_id() >> 5)) * 2;
 #pragma unroll
     for (int T = 0; T < NT; ++T) {
       float y[16], g2v[16], be2v[16];
@@ -1080,8 +1000,8 @@ void tailp_kernel(TailArgs p) {
 #pragma unroll
       for (int h2 = 0; h2 < 2; ++h2)
         __builtin_amdgcn_raw_buffer_store_b128(
-            u32x4{tl_pack2(y[8 * h2], y[8 * h2 + 1]), tl_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                  tl_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), tl_pack2(y[8 * h2 + 6], y[8 * h2 + 7])},
+            u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                  pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])},
             ors, row_off + 64 * T + 16 * h2, 0, 0);
     }
     mark(6);
@@ -1108,18 +1028,18 @@ __global__ void tail_pack_kernel(int D, long n_pieces, const bf16* __restrict__ 
   bf16 v[8];
   if (F < FPRE) {
     const int s = (int)(F / NT), T = (int)(F % NT);
-    const int n = tail_out_feat(T, m);
-    for (int j = 0; j < 8; ++j) v[j] = wo[(long)n * D + tail_in_feat(s, kh, j)];
+    const int n = out_feat(T, m);
+    for (int j = 0; j < 8; ++j) v[j] = wo[(long)n * D + in_feat(s, kh, j)];
   } else {
     const long g = F - FPRE;
     const int c = (int)(g / FPC), f = (int)(g % FPC);
     if (f < FW1) {
       const int s = f >> 1, t = f & 1;
       const long hid = (long)c * 64 + 32 * t + m;
-      for (int j = 0; j < 8; ++j) v[j] = w1[hid * D + tail_in_feat(s, kh, j)];
+      for (int j = 0; j < 8; ++j) v[j] = w1[hid * D + in_feat(s, kh, j)];
     } else {
       const int f2 = f - FW1, s2 = f2 / NT, T = f2 % NT;
-      const int n = tail_out_feat(T, m);
+      const int n = out_feat(T, m);
       for (int j = 0; j < 8; ++j) v[j] = w2g[(long)n * 4 * D + (long)c * 64 + tail_hid(s2, kh, j)];
     }
   }
@@ -1136,14 +1056,14 @@ __global__ void proj_pack_kernel(int D, long n_pieces, const bf16* __restrict__ 
   const int l = (int)(p % 64), m = l & 31, kh = l >> 5;
   const int c = (int)(F / FPRE), f = (int)(F % FPRE);
   const int s = f / NT, T = f % NT;
-  const long n = (long)c * D + tail_out_feat(T, m);
-  for (int j = 0; j < 8; ++j) out[p * 8 + j] = w[n * D + tail_in_feat(s, kh, j)];
+  const long n = (long)c * D + out_feat(T, m);
+  for (int j = 0; j < 8; ++j) out[p * 8 + j] = w[n * D + in_feat(s, kh, j)];
 }
 
 template <int D, int NC>
 static int launch_proj(const TailArgs& a, hipStream_t s) {
   auto kern = tail_kernel<D, false, TL_PF4, 0, true, NC>;
-  constexpr size_t lds = (size_t)TL_NSLOT * TL_SLAB + NC * D * 4;
+  constexpr size_t lds = (size_t)TL_NSLOT * SLAB_BYTES + NC * D * 4;
   static_assert(NC * D * 4 <= TL_VEC_LDS && lds <= 160 * 1024, "LDS budget");
   SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, TL_ROWS)), dim3(256), lds, s, a);
@@ -1169,9 +1089,8 @@ template <int D>
 static int launch_tailp(TailArgs a, hipStream_t s) {
   const long ntiles = cdiv(a.M, TL_ROWS);
   const int grid = (int)std::min<long>(ntiles, cu_count());
-  const int64_t dz = options().tail_desync;
-  a.desync = ntiles >= 8L * grid ? (dz >= 0 ? (int)dz : 25000 * D / 384 * D / 384) : 0;
-  constexpr size_t lds = (size_t)TP_NSLOT * TL_SLAB + 11 * D * 4;   // ring + [vec 8D | g1 | be1 | b_o]
+  a.desync = stagger_step(ntiles, 8L * grid, options().tail_desync, 25000 * D / 384 * D / 384);
+  constexpr size_t lds = (size_t)TP_NSLOT * SLAB_BYTES + 11 * D * 4;   // ring + [vec 8D | g1 | be1 | b_o]
   static_assert(lds <= 160 * 1024, "LDS budget");
   auto kern = tailp_kernel<D>;
   if (options().tail_variant == 7 && g_tail_stamps) {     // phase stamps (tools/tail_micro.py)
@@ -1191,13 +1110,11 @@ static int launch_tail(TailArgs a, hipStream_t s) {
   // registers of the one wave that uses it
   if constexpr (PRE && D == 384)
     if (var == 0 && options().tail_wide) {
-      const long nwg = cdiv(a.M, TL_ROWS);
-      const int64_t dz = options().tail_desync;
       // (first-round stagger 10 k cycles: tools/tailw_desync.py, two boxes: 1.409 / 1.403 ms vs
       // 1.454 / 1.399 at tail_kernel's 25 k and 1.444 without; r6: 4 k was 1 % faster alone
       // (tools/tailw_desync_sweep.py) but 0.7 % slower inside the bench step, 1.363 vs 1.353 ms,
       // profiles/r6_tail_desync_bench_ab.txt — 10 k kept)
-      const int desync = nwg >= 8 * 256 ? (dz >= 0 ? (int)dz : 10000) : 0;
+      const int desync = stagger_step(cdiv(a.M, TL_ROWS), 8 * 256, options().tail_desync, 10000);
       return tailw_launch(a.M, a.act, a.resid, a.out, a.ws, a.vec, a.b_o, a.g1, a.be1, a.eps, desync,
                           (int)options().tail_wide >= 2 ? (int)options().tail_wide - 1 : 0, s);
     }
@@ -1217,10 +1134,8 @@ static int launch_tail(TailArgs a, hipStream_t s) {
   // first-round phase step: only when every CU runs several rounds (the delay is paid once).
   // Default 1/8 of a block's ~200 k cycles at D = 384 (tools/tail_micro.py, M = 527 360:
   // 1.668 ms without, 1.611 / 1.593 / 1.602 ms at 12 k / 25 k / 40 k), scaled with the D^2 work
-  const long nwg = cdiv(a.M, TL_ROWS);
-  const int64_t dz = options().tail_desync;
-  a.desync = nwg >= 8 * 256 ? (dz >= 0 ? (int)dz : 25000 * D / 384 * D / 384) : 0;
-  constexpr size_t lds = (size_t)TL_NSLOT * TL_SLAB + 7 * D * 4;     // ring + b1, g1, be1, b_o
+  a.desync = stagger_step(cdiv(a.M, TL_ROWS), 8 * 256, options().tail_desync, 25000 * D / 384 * D / 384);
+  constexpr size_t lds = (size_t)TL_NSLOT * SLAB_BYTES + 7 * D * 4;     // ring + b1, g1, be1, b_o
   static_assert(7 * D * 4 <= TL_VEC_LDS && lds <= 160 * 1024, "LDS budget");
   SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, TL_ROWS)), dim3(256), lds, s, a);
@@ -1232,9 +1147,9 @@ static bool tail_d_ok(int D) { return D == 128 || D == 256 || D == 384; }
 
 static size_t tail_bytes(int D) {
   switch (D) {
-    case 128: return (size_t)TailShape<128>::NSLAB * TL_SLAB;
-    case 256: return (size_t)TailShape<256>::NSLAB * TL_SLAB;
-    case 384: return (size_t)TailShape<384>::NSLAB * TL_SLAB;
+    case 128: return (size_t)TailShape<128>::NSLAB * SLAB_BYTES;
+    case 256: return (size_t)TailShape<256>::NSLAB * SLAB_BYTES;
+    case 384: return (size_t)TailShape<384>::NSLAB * SLAB_BYTES;
     default: return 0;
   }
 }
@@ -1315,9 +1230,9 @@ extern "C" int snvrag_tail_ffn_forward(int64_t M, int D, const void* x1, void* o
 
 static size_t proj_bytes(int D, int NC) {
   switch (D) {
-    case 128: return (size_t)NC * TailShape<128>::NPRE * TL_SLAB;
-    case 256: return (size_t)NC * TailShape<256>::NPRE * TL_SLAB;
-    case 384: return (size_t)NC * TailShape<384>::NPRE * TL_SLAB;
+    case 128: return (size_t)NC * TailShape<128>::NPRE * SLAB_BYTES;
+    case 256: return (size_t)NC * TailShape<256>::NPRE * SLAB_BYTES;
+    case 384: return (size_t)NC * TailShape<384>::NPRE * SLAB_BYTES;
     default: return 0;
   }
 }
@@ -1350,8 +1265,7 @@ extern "C" int snvrag_proj_forward(int64_t M, int D, int NC, const void* x, cons
   int rc;
   if (D == 384 && options().proj_wide && (long)M * NC * D * 2 < 0x7fffffffL) {
     // the wide-row projection (tailw.hip): first-round stagger as the block tail's
-    const int64_t dz = options().sg_desync;
-    const int desync = cdiv(M, TL_ROWS) >= 8 * 256 ? (dz >= 0 ? (int)dz : 8000) : 0;
+    const int desync = stagger_step(cdiv(M, TL_ROWS), 8 * 256, options().sg_desync, 8000);
     rc = projw_launch((int)M, NC, x, wstream, bias, out, desync, s);
     if (rc) return rc;
     evlog_end(s, EV_GEMM, 2.0 * M * (double)D * D * NC);

@@ -25,10 +25,9 @@
 // The W fragment loads are inline asm with hand-counted s_waitcnt vmcnt (tw_younger): the
 // compiler sees no loads, so it neither drains them at loop edges nor reorders around them; the
 // MFMAs are inline asm too (fixed AGPR / VGPR accumulators), so every accumulator read waits for
-// tw_drain() (the compiler's hazard recognizer does not know these are MFMAs).
+// drain() (the compiler's hazard recognizer does not know these are MFMAs).
 #include "common.h"
-
-#include <utility>
+#include "mfma32.h"
 
 namespace snvrag {
 
@@ -37,7 +36,6 @@ namespace snvrag {
 #endif
 
 constexpr int TW_D = 384, TW_NT = 12, TW_KS = 24;
-constexpr int TW_FRAG = 1024;
 constexpr int TW_FPRE = TW_NT * TW_KS;               // W_o' fragments (288)
 constexpr int TW_FPC = 96;                           // fragments per 64-unit chunk: W1 48, W2' 48
 constexpr int TW_NFRAG = TW_FPRE + 24 * TW_FPC;      // whole stream (2592)
@@ -128,14 +126,9 @@ __host__ __device__ constexpr bool tw_ring_periodic() {
 static_assert(tw_ring_periodic(), "fragment ring registers periodic over the sections");
 static_assert(TW_B1_WAIT_END <= 63 && tw_younger(0) <= 63, "vmcnt range");
 
-template <typename Body, int... Is>
-__device__ __forceinline__ void tw_unroll(Body&& body, std::integer_sequence<int, Is...>) {
-  (body(std::integral_constant<int, Is>{}), ...);
-}
-// NOP: s_nop 1 ahead of the MFMA — hipcc pads nothing inside an asm string, and outside the FFN
-// loop (phase A, half-round 0, the last half-rounds) it stashes W fragments in AGPRs and reads one
-// back right before its MFMA (a VALU write of an operand: 2 wait states); the loop body has no such
-// write (tests/test_asm_hazards.py scans for it)
+// mfma32_asm's NOP (mfma32.h): outside the FFN loop (phase A, half-round 0, the last half-rounds)
+// hipcc stashes W fragments in AGPRs and reads one back right before its MFMA (a VALU write of an
+// operand: 2 wait states); the loop body has no such write (tests/test_asm_hazards.py scans for it)
 // TW_NOPMASK: which MFMA segments outside the FFN loop carry the s_nop (bit 0 phase A, bit 1 FFN1(0),
 // bit 2 the last FFN1 / FFN2 of the loop's tail, bit 3 FFN2(11)); the 32-row (G = 1) body always.
 // r6: only FFN1(0) gets a VALU write of an MFMA operand within 2 wait states without it (a scan of
@@ -143,31 +136,6 @@ __device__ __forceinline__ void tw_unroll(Body&& body, std::integer_sequence<int
 #ifndef TW_NOPMASK
 #define TW_NOPMASK 2
 #endif
-template <bool AGPR, bool NOP = true>
-__device__ __forceinline__ void tw_mfma(f32x16& c, const u32x4& a, const u32x4& b) {
-  if constexpr (AGPR && NOP)
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-  else if constexpr (AGPR)
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-  else if constexpr (NOP)
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-  else
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-// zero C operand: the accumulator's first k-step
-template <bool AGPR, bool NOP = true>
-__device__ __forceinline__ void tw_mfma0(f32x16& c, const u32x4& a, const u32x4& b) {
-  if constexpr (AGPR && NOP)
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
-  else if constexpr (AGPR)
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
-  else if constexpr (NOP)
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
-  else
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
-}
-// a 32x32x16 result is readable 18 wait states after issue
-__device__ __forceinline__ void tw_drain() { asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory"); }
 // the drain with the accumulators as operands: no read or register move of them (a compiler copy is
 // not a memory access and crossed the plain drain) can be scheduled before it
 __device__ __forceinline__ void tw_drain_o(f32x16 (&a)[3][4]) {
@@ -182,50 +150,14 @@ template <bool AGPR> __device__ __forceinline__ void tw_drain_h4(f32x16 (&h)[4])
   else
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" : "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]) :: "memory");
 }
-__device__ __forceinline__ int tw_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-__device__ __forceinline__ uint32_t tw_pack2(float a, float b) {
-  typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  const f2 v = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, b2));
-}
-__device__ __forceinline__ float tw_lrelu(float x) {
-  float r;
-  asm("v_mul_f32 %0, 0x3dcccccd, %1\n v_max_f32 %0, %1, %0" : "=&v"(r) : "v"(x));
-  return r;
-}
-typedef float tw_f2 __attribute__((ext_vector_type(2)));
-// the two bf16 of a packed word as floats (low half first)
-__device__ __forceinline__ tw_f2 tw_bf2(uint32_t w) { return tw_f2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)}; }
-__device__ __forceinline__ tw_f2 tw_lrelu2(tw_f2 x) {
-  const tw_f2 m = x * 0.1f;                           // one v_pk_mul_f32
+__device__ __forceinline__ f32x2 tw_lrelu2(f32x2 x) {
+  const f32x2 m = x * 0.1f;                           // one v_pk_mul_f32
   float a, b;
   asm("v_max_f32 %0, %1, %2" : "=v"(a) : "v"(x.x), "v"(m.x));
   asm("v_max_f32 %0, %1, %2" : "=v"(b) : "v"(x.y), "v"(m.y));
-  return tw_f2{a, b};
+  return f32x2{a, b};
 }
-__device__ __forceinline__ float tw_bf(const u32x4& v, int j) {
-  return (j & 1) ? __uint_as_float(v[j >> 1] & 0xffff0000u) : __uint_as_float(v[j >> 1] << 16);
-}
-__device__ __forceinline__ float tw_xsum32(float x) {
-  return x + __int_as_float(__builtin_amdgcn_ds_bpermute((tw_lane() ^ 32) << 2, __float_as_int(x)));
-}
-// 16 consecutive floats of an LDS table (reads and their wait in one statement)
-__device__ __forceinline__ void tw_ld16(uint32_t addr, float (&v)[16]) {
-  u32x4 r[4];
-  asm volatile(
-      "ds_read_b128 %0, %4 offset:0\n ds_read_b128 %1, %4 offset:16\n ds_read_b128 %2, %4 offset:32\n"
-      " ds_read_b128 %3, %4 offset:48\n s_waitcnt lgkmcnt(0)"
-      : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3])
-      : "v"(addr));
-#pragma unroll
-  for (int i = 0; i < 16; ++i) v[i] = __uint_as_float(r[i >> 2][i & 3]);
-}
-// the same by plain LDS reads (LN phases: no LDS-DMA is in flight there, so the compiler's waits
+// ld16 by plain LDS reads (LN phases: no LDS-DMA is in flight there, so the compiler's waits
 // count only these reads and it may issue the next tile's reads under this tile's math)
 __device__ __forceinline__ void tw_ld16p(const char* p, float (&v)[16]) {
 #pragma unroll
@@ -290,40 +222,35 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
   auto stamp = [&](int i) {
     if constexpr (VAR & 1) st[i] = __builtin_amdgcn_s_memtime();
   };
-  // first-round stagger (tail.hip): later rounds' prologue bursts overlap other CUs' MFMAs
-  if (p.desync > 0 && blockIdx.x < 256) {
-    const long wait = (long)p.desync * ((blockIdx.x >> 3) & 7);
-    const long t0 = (long)__builtin_amdgcn_s_memtime();
-    while ((long)__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(16);
-  }
+  if (p.desync > 0 && blockIdx.x < 256) stagger_wait(p.desync);   // first-round stagger (mfma32.h)
   stamp(0);
   const uint32_t lds0 = lds_addr(smem);
-  int lane16 = tw_lane() * 16;                        // (lane-derived values are re-made from a fresh
+  int lane16 = lane_id() * 16;                        // (lane-derived values are re-made from a fresh
   asm volatile("" : "+v"(lane16));                    //  v_mbcnt where used: kept live across the FFN they spill)
 
   // ---- prologue: att -> X by LDS-DMA (wave w: token group w, k16 steps in order; lane (n, kh) of
-  // piece s reads att[32 w + n][tail_in_feat(s, kh, 0 .. 7)]), the first W steps, the residual rows
+  // piece s reads att[32 w + n][in_feat(s, kh, 0 .. 7)]), the first W steps, the residual rows
   // (VGPRs, used by LN1), the LN1 tables -> H
   const i32x4 ars = dma_rsrc(p.att + row0 * D, ((long)p.M - row0) * D * 2);   // rows >= M read as 0
-  const i32x4 wrs = dma_rsrc(p.ws, (long)TW_NFRAG * TW_FRAG);
+  const i32x4 wrs = dma_rsrc(p.ws, (long)TW_NFRAG * FRAG_BYTES);
   const i32x4 brs = dma_rsrc(p.vec, 4L * D * 4);                             // b1
   {
-    const int l = tw_lane();
+    const int l = lane_id();
     const int voff = (32 * wave + (l & 31)) * (D * 2) + 32 * (l >> 5);
     if (wave < G) {
 #pragma unroll
       for (int s = 0; s < TW_KS; ++s)
-        dma_x4(ars, lds0 + TW_X + (s * 4 + wave) * TW_FRAG, voff, 64 * (s >> 1) + 16 * (s & 1));
+        dma_x4(ars, lds0 + TW_X + (s * 4 + wave) * FRAG_BYTES, voff, 64 * (s >> 1) + 16 * (s & 1));
     }
   }
   u32x4 wf[TW_RING];                                 // W fragment ring
   // W fragment F of the stream into register r (soffset: scalar)
   // (compiler-visible loads: its waitcnt pass places the waits before every read of the register —
   // hand-counted asm loads were seen copied into AGPRs by the register allocator before they landed)
-  const __amdgpu_buffer_rsrc_t wrb = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, TW_NFRAG * TW_FRAG, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrb = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, TW_NFRAG * FRAG_BYTES, 0x00020000);
   // (diagnostic VAR bit 1: every load reads fragment F % 12 — a cache-resident 12 KiB, results wrong)
   auto loadW = [&](u32x4& r, int F) {
-    r = __builtin_amdgcn_raw_buffer_load_b128(wrb, lane16, ((VAR & 2) ? F % 12 : F) * TW_FRAG, 0);
+    r = __builtin_amdgcn_raw_buffer_load_b128(wrb, lane16, ((VAR & 2) ? F % 12 : F) * FRAG_BYTES, 0);
   };
   // stream offsets: FFN1(h) step i = wave w's tile of chunk 4 (h >> 1) + w, half h & 1;
   // FFN2(h) step u, tile t = chunk 4 (h >> 1) + u / 2, k16 step 2 (h & 1) + u % 2, tile 3w + t
@@ -339,12 +266,12 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
     else if constexpr (n < 96) loadW(wf[n % TW_RING], f_ffn1(0, n - 72));
     else loadW(wf[n % TW_RING], f_ffn1(1, n - 96));
   };
-  tw_unroll([&](auto nc) { issue_a(nc); }, std::make_integer_sequence<int, TW_AH>{});
+  unroll([&](auto nc) { issue_a(nc); }, std::make_integer_sequence<int, TW_AH>{});
   u32x4 rr[3][4][2];                                 // residual x: tile t, group g, half h2
   // (LATE_RES: issued after phase A step TW_RES_STEP's W loads instead of here — the prologue's HBM
   // burst halves; the W waits after it then also wait for these rows, in-order vmcnt)
   auto load_res = [&]() {
-    const int l = tw_lane();
+    const int l = lane_id();
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       long r = row0 + 32 * g + (l & 31);
@@ -379,26 +306,26 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
   f32x16 acc[3][4];
   u32x4 bq[3][4];                                     // B fragments, read two k16 steps ahead
   auto rdB = [&](uint32_t base, int blk) -> u32x4 {
-    return *reinterpret_cast<const u32x4*>(smem + base + blk * TW_FRAG + lane16);
+    return *reinterpret_cast<const u32x4*>(smem + base + blk * FRAG_BYTES + lane16);
   };
   // (B fragments one step ahead in two buffers here: 12 MFMAs per step cover the LDS latency, and
   // a third buffer beside the residual rows pushed the W fragments into AGPR copies taken before
   // their loads had landed)
 #pragma unroll
   for (int g = 0; g < G; ++g) bq[0][g] = rdB(TW_X, g);
-  tw_unroll([&](auto qc) {
+  unroll([&](auto qc) {
     constexpr int q = decltype(qc)::value, n0 = 3 * q;
     tw_wait3<tw_younger(q)>(wf[n0 % TW_RING], wf[(n0 + 1) % TW_RING], wf[(n0 + 2) % TW_RING]);
 #pragma unroll
     for (int g = 0; g < G; ++g) {
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
-        if constexpr (q == 0) tw_mfma0<true, NOPA>(acc[t][g], wf[(n0 + t) % TW_RING], bq[q & 1][g]);
-        else tw_mfma<true, NOPA>(acc[t][g], wf[(n0 + t) % TW_RING], bq[q & 1][g]);
+        if constexpr (q == 0) mfma32_asm0<true, NOPA>(acc[t][g], wf[(n0 + t) % TW_RING], bq[q & 1][g]);
+        else mfma32_asm<true, NOPA>(acc[t][g], wf[(n0 + t) % TW_RING], bq[q & 1][g]);
       }
       if constexpr (q + 1 < TW_KS) bq[(q + 1) & 1][g] = rdB(TW_X, (q + 1) * 4 + g);
       if (g == GI)
-        tw_unroll([&](auto tc) { issue_a(std::integral_constant<int, n0 + TW_AH + decltype(tc)::value>{}); },
+        unroll([&](auto tc) { issue_a(std::integral_constant<int, n0 + TW_AH + decltype(tc)::value>{}); },
                   std::make_integer_sequence<int, 3>{});
     }
     if constexpr (LATE_RES && q == TW_RES_STEP) load_res();
@@ -410,12 +337,12 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
   // ---- LN1 over the 4 waves' features: v = ao + b_o + x; per-wave (sum, sumsq) -> LDS
   float2* s1 = reinterpret_cast<float2*>(smem + TW_H + 8 * 1024);          // [wave][128 rows]
   {
-    const uint32_t tb = lds0 + TW_H + 64 * (tw_lane() >> 5);
+    const uint32_t tb = lds0 + TW_H + 64 * (lane_id() >> 5);
 #if TW_PACKED_LN
     // (packed f32 math: pairs of features per v_pk_* instruction)
-    tw_f2 s2v[4], q2v[4];
+    f32x2 s2v[4], q2v[4];
 #pragma unroll
-    for (int g = 0; g < G; ++g) s2v[g] = q2v[g] = tw_f2{0.f, 0.f};
+    for (int g = 0; g < G; ++g) s2v[g] = q2v[g] = f32x2{0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       float bo[16];
@@ -424,8 +351,8 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
       for (int g = 0; g < G; ++g)
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const tw_f2 v = tw_f2{acc[t][g][2 * e], acc[t][g][2 * e + 1]} + tw_f2{bo[2 * e], bo[2 * e + 1]} +
-                          tw_bf2(rr[t][g][e >> 2][e & 3]);
+          const f32x2 v = f32x2{acc[t][g][2 * e], acc[t][g][2 * e + 1]} + f32x2{bo[2 * e], bo[2 * e + 1]} +
+                          bf_pair(rr[t][g][e >> 2][e & 3]);
           acc[t][g][2 * e] = v.x;
           acc[t][g][2 * e + 1] = v.y;
           s2v[g] += v;
@@ -448,7 +375,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
       for (int g = 0; g < G; ++g)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const float v = acc[t][g][i] + bo[i] + tw_bf(rr[t][g][i >> 3], i & 7);
+          const float v = acc[t][g][i] + bo[i] + bf_at(rr[t][g][i >> 3], i & 7);
           acc[t][g][i] = v;
           sum[g] += v;
           sq[g] = fmaf(v, v, sq[g]);
@@ -459,17 +386,17 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
     for (int t = 0; t < 3; ++t)
 #pragma unroll
       for (int g = 0; g < G; ++g) {}   // v back in AGPRs
-    const int l = tw_lane();
+    const int l = lane_id();
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-      sum[g] = tw_xsum32(sum[g]);
-      sq[g] = tw_xsum32(sq[g]);
+      sum[g] = xsum32(sum[g]);
+      sq[g] = xsum32(sq[g]);
       s1[wave * 128 + 32 * g + (l & 31)] = make_float2(sum[g], sq[g]);
     }
   }
   tw_barrier();                                       // every wave past phase A: X is free for x1
   {
-    const int l = tw_lane();
+    const int l = lane_id();
     const uint32_t tb = lds0 + TW_H + 64 * (l >> 5);
     float mean[4], rstd[4];
 #pragma unroll
@@ -497,8 +424,8 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
         const float nmr = -mean[g] * rstd[g];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const tw_f2 z = (tw_f2{acc[t][g][2 * e], acc[t][g][2 * e + 1]} * rstd[g] + nmr) * tw_f2{gg[2 * e], gg[2 * e + 1]} +
-                          tw_f2{bb[2 * e], bb[2 * e + 1]};
+          const f32x2 z = (f32x2{acc[t][g][2 * e], acc[t][g][2 * e + 1]} * rstd[g] + nmr) * f32x2{gg[2 * e], gg[2 * e + 1]} +
+                          f32x2{bb[2 * e], bb[2 * e + 1]};
           y[2 * e] = z.x;
           y[2 * e + 1] = z.y;
         }
@@ -509,9 +436,9 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
         // x1 features 32T + 16hh + 8h2 + j = k16 step 2T + h2, lane slot (n, kh = hh)
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2)
-          *reinterpret_cast<u32x4*>(smem + TW_X + ((2 * T + h2) * 4 + g) * TW_FRAG + lane16) =
-              u32x4{tw_pack2(y[8 * h2], y[8 * h2 + 1]), tw_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                    tw_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), tw_pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
+          *reinterpret_cast<u32x4*>(smem + TW_X + ((2 * T + h2) * 4 + g) * FRAG_BYTES + lane16) =
+              u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                    pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
       }
     }
   }
@@ -543,7 +470,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
   const __amdgpu_buffer_rsrc_t b1b = __builtin_amdgcn_make_buffer_rsrc((void*)p.vec, (short)0, 4 * D * 4, 0x00020000);
   auto b1_load = [&](int h) {                         // b1[64 c' + 32 (h & 1) + 8 r + 4 hh .. + 3]
     const int so = 4 * (64 * (4 * (h >> 1) + wave) + 32 * (h & 1));
-    const int vo = 16 * (tw_lane() >> 5);
+    const int vo = 16 * (lane_id() >> 5);
 #pragma unroll
     for (int r = 0; r < 4; ++r) b1v[r] = __builtin_amdgcn_raw_buffer_load_b128(b1b, vo + 32 * r, so, 0);
   };
@@ -562,7 +489,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
     constexpr int g = k >> 1, j = k & 1;
     if constexpr (g < G) {
       const f32x16& a = Q ? ha[g] : hv[g];
-      tw_unroll([&](auto vc) {
+      unroll([&](auto vc) {
         constexpr int v = decltype(vc)::value;
         if constexpr (v * (TW_EP - 2) / 8 == pc) {
           // (LeakyReLU as plain code: the inline-asm form made hipcc pad an s_nop after every one)
@@ -575,10 +502,10 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
       }, std::make_integer_sequence<int, 8>{});
       if constexpr (pc == TW_EP - 2) {
 #pragma unroll
-        for (int e2 = 0; e2 < 4; ++e2) epk[e2] = tw_pack2(ex[2 * e2], ex[2 * e2 + 1]);
+        for (int e2 = 0; e2 < 4; ++e2) epk[e2] = pack2(ex[2 * e2], ex[2 * e2 + 1]);
       }
       if constexpr (pc == TW_EP - 1)
-        *reinterpret_cast<u32x4*>(smem + TW_H + Q * 32768 + ((wave * 2 + j) * 4 + g) * TW_FRAG + lane16) =
+        *reinterpret_cast<u32x4*>(smem + TW_H + Q * 32768 + ((wave * 2 + j) * 4 + g) * FRAG_BYTES + lane16) =
             u32x4{epk[0], epk[1], epk[2], epk[3]};
     }
   };
@@ -597,17 +524,17 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
     constexpr int P = decltype(p_tag)::value, Q0 = decltype(q0_tag)::value;
     constexpr bool EPI = decltype(epi_tag)::value, NOP = decltype(nop_tag)::value, B1 = decltype(b1_tag)::value;
     constexpr int F0 = tw_f0(Q0);
-    tw_unroll([&](auto ic) {
+    unroll([&](auto ic) {
       constexpr int i = decltype(ic)::value, q = Q0 + i, n = F0 + i;
       tw_wait1<tw_wait_of(q)>(wf[n % TW_RING]);
-      tw_unroll([&](auto gc) {
+      unroll([&](auto gc) {
         constexpr int g = decltype(gc)::value;
         if constexpr (P == 0) {
-          if constexpr (i == 0) tw_mfma0<false, NOP>(hv[g], wf[n % TW_RING], bq[(i + 2) % 3][g]);
-          else tw_mfma<false, NOP>(hv[g], wf[n % TW_RING], bq[(i + 2) % 3][g]);
+          if constexpr (i == 0) mfma32_asm0<false, NOP>(hv[g], wf[n % TW_RING], bq[(i + 2) % 3][g]);
+          else mfma32_asm<false, NOP>(hv[g], wf[n % TW_RING], bq[(i + 2) % 3][g]);
         } else {
-          if constexpr (i == 0) tw_mfma0<true, NOP>(ha[g], wf[n % TW_RING], bq[(i + 2) % 3][g]);
-          else tw_mfma<true, NOP>(ha[g], wf[n % TW_RING], bq[(i + 2) % 3][g]);
+          if constexpr (i == 0) mfma32_asm0<true, NOP>(ha[g], wf[n % TW_RING], bq[(i + 2) % 3][g]);
+          else mfma32_asm<true, NOP>(ha[g], wf[n % TW_RING], bq[(i + 2) % 3][g]);
         }
         // (diagnostic VAR bit 2: FFN1 reads no B fragments — stale operands, no LDS traffic)
         if constexpr (i + 2 < 24 && !(VAR & 4)) bq[(i + 4) % 3][g] = rdB(TW_X, (i + 2) * 4 + g);
@@ -645,14 +572,14 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
       bq[0][g] = rdB(HB, g);
       bq[1][g] = rdB(HB, 4 + g);
     }
-    tw_unroll([&](auto uc) {
+    unroll([&](auto uc) {
       constexpr int u = decltype(uc)::value, q = Q0 + u, n0 = F0 + 3 * u;
       tw_wait3<tw_wait_of(q)>(wf[n0 % TW_RING], wf[(n0 + 1) % TW_RING], wf[(n0 + 2) % TW_RING]);
-      tw_unroll([&](auto gc) {
+      unroll([&](auto gc) {
         constexpr int g = decltype(gc)::value;
-        tw_unroll([&](auto tc) {
+        unroll([&](auto tc) {
           constexpr int t = decltype(tc)::value, x = 3 * G * u + 3 * g + t;
-          tw_mfma<true, NOP>(acc[t][g], wf[(n0 + t) % TW_RING], bq[u % 3][g]);
+          mfma32_asm<true, NOP>(acc[t][g], wf[(n0 + t) % TW_RING], bq[u % 3][g]);
           if constexpr (EPI) {
             epi_piece(std::integral_constant<int, x / (3 * G)>{}, std::integral_constant<int, 1 - P>{},
                       std::integral_constant<int, x % (3 * G)>{});
@@ -664,12 +591,12 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
         if constexpr (g == GI) {
           if constexpr (FINAL) {
             if constexpr (n0 + TW_AH < TW_NFRAGW)
-              tw_unroll([&](auto tc) {
+              unroll([&](auto tc) {
                 constexpr int m = n0 + TW_AH + decltype(tc)::value;
                 if constexpr (m < TW_NFRAGW) loadW(wf[m % TW_RING], f_ffn2(h, (m - F0) / 3, (m - F0) % 3));
               }, std::make_integer_sequence<int, 3>{});
           } else {
-            tw_unroll([&](auto tc) {
+            unroll([&](auto tc) {
               issue_it(std::integral_constant<int, 24 + 3 * u + TW_AH + decltype(tc)::value>{}, h + 1, last_tag);
             }, std::make_integer_sequence<int, 3>{});
           }
@@ -724,8 +651,8 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
     ffn_barrier();
     seg2(10, P0{}, IQ2{}, T1{}, T0{}, TNT{}, T0{});
     // the epilogue of half-round 11, then its FFN2
-    tw_unroll([&](auto kc) {                          // (unit by unit: a unit's pieces share ex / epk)
-      tw_unroll([&](auto pc) { epi_piece(kc, P1{}, pc); }, std::make_integer_sequence<int, TW_EP>{});
+    unroll([&](auto kc) {                          // (unit by unit: a unit's pieces share ex / epk)
+      unroll([&](auto pc) { epi_piece(kc, P1{}, pc); }, std::make_integer_sequence<int, TW_EP>{});
     }, std::make_integer_sequence<int, 8>{});
     ffn_barrier();
   } else {
@@ -757,7 +684,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int pc = wave + 4 * j;
-      if (pc < 6) dma_x4(vrs, lds0 + TW_H + pc * TW_FRAG, lane16, pc * TW_FRAG);
+      if (pc < 6) dma_x4(vrs, lds0 + TW_H + pc * FRAG_BYTES, lane16, pc * FRAG_BYTES);
     }
   }
   seg2(11, std::integral_constant<int, 1>{}, std::integral_constant<int, TW_QF>{}, std::false_type{},
@@ -776,18 +703,18 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
   float2* s3 = reinterpret_cast<float2*>(smem + TW_H + 12 * 1024);
   // (H half 0 holds the tables, DMA'd during FFN2(11), and the statistics; FFN2(11) reads half 1)
   {
-    const int l = tw_lane();
+    const int l = lane_id();
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-      st1[g] = tw_xsum32(st1[g]);
-      st2[g] = tw_xsum32(st2[g]);
+      st1[g] = xsum32(st1[g]);
+      st2[g] = xsum32(st2[g]);
       s2[wave * 128 + 32 * g + (l & 31)] = make_float2(st1[g], st2[g]);
     }
   }
   tw_barrier();
   float hm[4], hr[4];
   {
-    const int l = tw_lane();
+    const int l = lane_id();
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       float a = 0.f, b = 0.f;
@@ -801,13 +728,13 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
       hr[g] = 1.0f / sqrtf(fmaxf(b * (1.0f / (4 * D)) - hm[g] * hm[g], 0.f) + p.eps);
     }
   }
-  const uint32_t eb = lds0 + TW_H + 64 * (tw_lane() >> 5);
+  const uint32_t eb = lds0 + TW_H + 64 * (lane_id() >> 5);
   {
 #if TW_PACKED_LN
     // u = hr (acc - hm c1) + b2' = acc hr + (b2' - hm hr c1), in pairs (v_pk_fma_f32)
-    tw_f2 s2v[4], q2v[4];
+    f32x2 s2v[4], q2v[4];
 #pragma unroll
-    for (int g = 0; g < G; ++g) s2v[g] = q2v[g] = tw_f2{0.f, 0.f};
+    for (int g = 0; g < G; ++g) s2v[g] = q2v[g] = f32x2{0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       const int T = 3 * wave + t;
@@ -820,9 +747,9 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
         const float nhh = -hm[g] * hr[g];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const tw_f2 k = tw_f2{c1[2 * e], c1[2 * e + 1]} * nhh + tw_f2{b2[2 * e], b2[2 * e + 1]};
-          const tw_f2 u = tw_lrelu2(tw_f2{acc[t][g][2 * e], acc[t][g][2 * e + 1]} * hr[g] + k);
-          const tw_f2 v = u + tw_bf2((e < 4 ? xa : xb)[e & 3]);
+          const f32x2 k = f32x2{c1[2 * e], c1[2 * e + 1]} * nhh + f32x2{b2[2 * e], b2[2 * e + 1]};
+          const f32x2 u = tw_lrelu2(f32x2{acc[t][g][2 * e], acc[t][g][2 * e + 1]} * hr[g] + k);
+          const f32x2 v = u + bf_pair((e < 4 ? xa : xb)[e & 3]);
           acc[t][g][2 * e] = v.x;
           acc[t][g][2 * e + 1] = v.y;
           s2v[g] += v;
@@ -850,8 +777,8 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           float u = hr[g] * fmaf(-hm[g], c1[i], acc[t][g][i]) + b2[i];
-          u = tw_lrelu(u);
-          const float v = u + tw_bf(i < 8 ? xa : xb, i & 7);
+          u = lrelu(u);
+          const float v = u + bf_at(i < 8 ? xa : xb, i & 7);
           acc[t][g][i] = v;
           sum[g] += v;
           sq[g] = fmaf(v, v, sq[g]);
@@ -863,17 +790,17 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
     for (int t = 0; t < 3; ++t)
 #pragma unroll
       for (int g = 0; g < G; ++g) {}
-    const int l = tw_lane();
+    const int l = lane_id();
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-      sum[g] = tw_xsum32(sum[g]);
-      sq[g] = tw_xsum32(sq[g]);
+      sum[g] = xsum32(sum[g]);
+      sq[g] = xsum32(sq[g]);
       s3[wave * 128 + 32 * g + (l & 31)] = make_float2(sum[g], sq[g]);
     }
   }
   tw_barrier();
   {
-    const int l = tw_lane();
+    const int l = lane_id();
     float mean[4], rstd[4];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -901,8 +828,8 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
 #pragma unroll
 #if TW_PACKED_LN
         for (int e = 0; e < 8; ++e) {
-          const tw_f2 z = (tw_f2{acc[t][g][2 * e], acc[t][g][2 * e + 1]} * rstd[g] + nmr) * tw_f2{g2[2 * e], g2[2 * e + 1]} +
-                          tw_f2{be2[2 * e], be2[2 * e + 1]};
+          const f32x2 z = (f32x2{acc[t][g][2 * e], acc[t][g][2 * e + 1]} * rstd[g] + nmr) * f32x2{g2[2 * e], g2[2 * e + 1]} +
+                          f32x2{be2[2 * e], be2[2 * e + 1]};
           y[2 * e] = z.x;
           y[2 * e + 1] = z.y;
         }
@@ -913,8 +840,8 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2)
             *reinterpret_cast<u32x4*>(p.out + r * D + 32 * T + 16 * (l >> 5) + 8 * h2) =
-                u32x4{tw_pack2(y[8 * h2], y[8 * h2 + 1]), tw_pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                      tw_pack2(y[8 * h2 + 4], y[8 * h2 + 5]), tw_pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
+                u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                      pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
         }
       }
     }
@@ -984,30 +911,26 @@ void projw_kernel(PwArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long row0 = (long)blockIdx.x * 128;
-  if (p.desync > 0 && blockIdx.x < 256) {
-    const long wait = (long)p.desync * ((blockIdx.x >> 3) & 7);
-    const long t0 = (long)__builtin_amdgcn_s_memtime();
-    while ((long)__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(16);
-  }
+  if (p.desync > 0 && blockIdx.x < 256) stagger_wait(p.desync);   // first-round stagger (mfma32.h)
   const uint32_t lds0 = lds_addr(smem);
-  int lane16 = tw_lane() * 16;
+  int lane16 = lane_id() * 16;
   asm volatile("" : "+v"(lane16));
   const i32x4 xrs = dma_rsrc(p.x + row0 * D, ((long)p.M - row0) * D * 2);     // rows >= M read as 0
   {
-    const int l = tw_lane();
+    const int l = lane_id();
     const int voff = (32 * wave + (l & 31)) * (D * 2) + 32 * (l >> 5);
 #pragma unroll
     for (int s = 0; s < KS; ++s)
-      dma_x4(xrs, lds0 + TW_X + (s * 4 + wave) * TW_FRAG, voff, 64 * (s >> 1) + 16 * (s & 1));
+      dma_x4(xrs, lds0 + TW_X + (s * 4 + wave) * FRAG_BYTES, voff, 64 * (s >> 1) + 16 * (s & 1));
   }
   const int nfr = p.NC * TW_FPRE;
-  const __amdgpu_buffer_rsrc_t wrb = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, nfr * TW_FRAG, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrb = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, nfr * FRAG_BYTES, 0x00020000);
   u32x4 wf[TW_RING];
   // fragment n of this wave's stream: chunk n / 72, k16 step (n % 72) / 3, tile 3w + n % 3 (past the
   // last chunk: the last chunk again, never consumed)
   auto loadW = [&](u32x4& r, int c, int n72) {
     const int cc = c < p.NC ? c : p.NC - 1;
-    r = __builtin_amdgcn_raw_buffer_load_b128(wrb, lane16, (cc * TW_FPRE + (n72 / 3) * NT + 3 * wave + n72 % 3) * TW_FRAG, 0);
+    r = __builtin_amdgcn_raw_buffer_load_b128(wrb, lane16, (cc * TW_FPRE + (n72 / 3) * NT + 3 * wave + n72 % 3) * FRAG_BYTES, 0);
   };
 #pragma unroll
   for (int n = 0; n < TW_AH; ++n) loadW(wf[n], 0, n);
@@ -1015,7 +938,7 @@ void projw_kernel(PwArgs p) {
   for (int i = threadIdx.x; i < p.NC * D; i += 256) bs[i] = p.bias[i];
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the x image (LDS-DMA) landed
   tw_barrier();
-  auto rdB = [&](int blk) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + TW_X + blk * TW_FRAG + lane16); };
+  auto rdB = [&](int blk) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + TW_X + blk * FRAG_BYTES + lane16); };
   const long o_bytes = ((long)p.M - row0) * p.NC * D * 2;
   const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(p.out + row0 * p.NC * D), (short)0, (int)(o_bytes < 0x7fffffffL ? o_bytes : 0x7fffffffL), 0x00020000);
@@ -1025,14 +948,14 @@ void projw_kernel(PwArgs p) {
   for (int c = 0; c < p.NC; ++c) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) bq[0][g] = rdB(g);
-    tw_unroll([&](auto sc) {
+    unroll([&](auto sc) {
       constexpr int s = decltype(sc)::value, n0 = 3 * s;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
-          if constexpr (s == 0) tw_mfma0<true, false>(acc[t][g], wf[(n0 + t) % TW_RING], bq[s & 1][g]);
-          else tw_mfma<true, false>(acc[t][g], wf[(n0 + t) % TW_RING], bq[s & 1][g]);
+          if constexpr (s == 0) mfma32_asm0<true, false>(acc[t][g], wf[(n0 + t) % TW_RING], bq[s & 1][g]);
+          else mfma32_asm<true, false>(acc[t][g], wf[(n0 + t) % TW_RING], bq[s & 1][g]);
         }
         if constexpr (s + 1 < KS) bq[(s + 1) & 1][g] = rdB((s + 1) * 4 + g);
         if (g == 1) {
@@ -1050,13 +973,13 @@ void projw_kernel(PwArgs p) {
     }, std::make_integer_sequence<int, KS>{});
     tw_drain_o(acc);
     // + bias -> bf16 -> out[row][c D + 32 T + 16 hh .. + 15]
-    const int l = tw_lane();
+    const int l = lane_id();
     const uint32_t bb = lds0 + TW_H + 4 * (c * D + 16 * (l >> 5));
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       const int T = 3 * wave + t;
       float bv[16];
-      tw_ld16(bb + 4 * 32 * T, bv);
+      ld16(bb + 4 * 32 * T, bv);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int ro = ((32 * g + (l & 31)) * p.NC * D + c * D + 32 * T + 16 * (l >> 5)) * 2;
@@ -1065,8 +988,8 @@ void projw_kernel(PwArgs p) {
           float y[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) y[j] = acc[t][g][8 * h2 + j] + bv[8 * h2 + j];
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{tw_pack2(y[0], y[1]), tw_pack2(y[2], y[3]), tw_pack2(y[4], y[5]),
-                                                       tw_pack2(y[6], y[7])},
+          __builtin_amdgcn_raw_buffer_store_b128(u32x4{pack2(y[0], y[1]), pack2(y[2], y[3]), pack2(y[4], y[5]),
+                                                       pack2(y[6], y[7])},
                                                  ors, ro + 16 * h2, 0, 0);
         }
       }

@@ -793,6 +793,24 @@ def test_gemm256_derive_pack_matches_pack():
     assert torch.equal(outs[2], kk.gemm256_pack(wt.t().to(torch.bfloat16)))
 
 
+@pytest.mark.parametrize("D,N", [(128, 64), (384, 128)])
+def test_sgemm_derive_pack_matches_pack(D, N):
+    """snvrag_derive kind DERIVE_SGPACK from f32 masters (plain, two row-stacked parts, and a
+    transposed view — the forms the training path packs) == snvrag_sgemm_pack of the bf16-rounded
+    matrix, byte for byte.  N = 64 is one tile pair, the smallest stream."""
+    g = torch.Generator(device="cpu").manual_seed(6)
+    w = torch.randn(N, D, generator=g).to(DEV)
+    w1, w2 = torch.randn(N // 2, D, generator=g).to(DEV), torch.randn(N // 2, D, generator=g).to(DEV)
+    wt = torch.randn(D, N, generator=g).to(DEV)                    # [D, N]: pack W = wt^T
+    kk = K()
+    srcs = [[w], [w1, w2], [wt.t()]]
+    refs = [kk.sgemm_pack(torch.cat(s).to(torch.bfloat16)) for s in srcs]
+    outs = [torch.empty_like(r) for r in refs]
+    kk.derive(kk.derive_table([kk.derive_job(kk.DERIVE_SGPACK, s, o) for s, o in zip(srcs, outs)], DEV))
+    for i, (o, r) in enumerate(zip(outs, refs)):
+        assert torch.equal(o, r), i
+
+
 @pytest.mark.parametrize("groups", [4, 5, 6, 7, 8])
 def test_gemm256_row_groups_bit_identical(groups):
     """Every workgroup height (option g2_groups: 32 x 4 .. 8 rows; the default picks it by M) and
