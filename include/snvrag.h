@@ -817,6 +817,29 @@ int snvrag_bgzf_inflate(const uint8_t* comp, int64_t comp_bytes, const int64_t* 
                         int64_t n_blocks, uint8_t* text, int64_t text_bytes, int32_t* status, void* stream);
 int snvrag_text_last_newline(const uint8_t* text, int64_t nbytes, int64_t* out, void* stream);
 
+/* Device deflate into BGZF members (csrc/deflate.hip; the bgzip pass over the reference writer's output, which
+ * every user of the plain imputed.vcf runs on the host).  The compressor is csrc/deflate_core.h: LZ77 matches
+ * (length 3 .. 258, distance at most 32 768, inside the member) found through a hash table, dynamic Huffman
+ * codes per sub-block of 8 192 positions, the stored form where the coded one would be larger.  The bytes are
+ * a function of the input bytes alone (no dependence on lane order, wave count or grid position) and equal
+ * those of the host build of the same text.
+ *
+ * snvrag_bgzf_deflate: text[0, nbytes) is cut into n_blocks = ceil(nbytes / block_size) pieces of block_size
+ *   bytes (the last may be shorter); piece b becomes one complete BGZF member (header with the BC subfield,
+ *   raw deflate payload, CRC-32, ISIZE) at members + 65536 b, its length in member_len[b] (at most 65 536).
+ *   Bytes of a slot past the member's length are not touched.  text may have any alignment; members 16-byte
+ *   aligned, 65536 n_blocks bytes; member_len i32 [n_blocks].  One workgroup per member.
+ *   Refused with no launch: a null pointer, nbytes < 0 or >= 2^31, block_size outside [1, 0xff00], members
+ *   not 16-byte aligned.  nbytes == 0 launches nothing and returns 0.
+ * snvrag_bgzf_pack: the members of n_blocks slots copied back to back into out: an exclusive scan of
+ *   member_len, then 16-byte pieces to the aligned part of every destination.  *total (device i64, 8-byte
+ *   aligned) = the sum of member_len.  If the sum exceeds out_bytes, or a length lies outside [0, 65536],
+ *   nothing is written and *total = -1.  No float and no atomics. */
+int snvrag_bgzf_deflate(const uint8_t* text, int64_t nbytes, int64_t block_size, uint8_t* members,
+                        int32_t* member_len, void* stream);
+int snvrag_bgzf_pack(const uint8_t* members, const int32_t* member_len, int64_t n_blocks, uint8_t* out,
+                     int64_t out_bytes, int64_t* total, void* stream);
+
 /* self tests of MFMA operand/accumulator layouts used by the kernels (GPU only):
  * returns 0 when the i8 / bf16 / f32 MFMA maps match the CPU product. */
 int snvrag_selftest_mfma(void* stream);

@@ -164,6 +164,29 @@ class BgzfWriter:
         self.close()
 
 
+def deflate_device(data, block_size: int = 0xff00, device=None) -> bytes:
+    """The BGZF members of the bytes-like ``data``, ``block_size`` input bytes each, deflated and packed on the
+    GPU (csrc/deflate.hip; the compressor is csrc/deflate_core.h), without the EOF block.  The bytes depend on
+    ``data`` and ``block_size`` alone."""
+    import numpy as np
+    import torch
+    from .. import kernels as K
+    if not 1 <= block_size <= 0xff00:
+        raise ValueError(f"deflate_device: block_size {block_size} must lie in [1, 0xff00]")
+    mv = memoryview(data).cast("B")
+    if len(mv) == 0:
+        return b""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        text = torch.from_numpy(np.frombuffer(mv, np.uint8).copy()).to(dev)
+        members, member_len = K.bgzf_deflate(text, len(mv), block_size)
+        out = torch.empty(len(mv) + 31 * members.shape[0], device=dev, dtype=torch.uint8)   # a member adds at most 31
+        total = int(K.bgzf_pack(members, member_len, out).item())
+        if total < 0:
+            raise RuntimeError("deflate_device: the members exceed their bound")
+        return out[:total].cpu().numpy().tobytes()
+
+
 # ------------------------------------------------------------------------------------- the specification --
 class _Bits:
     """LSB-first bits of ``data``; bits past its end read as zero, ``over()`` once the position passed it."""

@@ -35,8 +35,8 @@ tail straight into the text buffer, the chunk is cut at its last newline by a de
 index, parse and pack steps run unchanged.  Only the few blocks that hold the header are inflated on the host.
 A file that is not BGZF (plain text, a single-member gzip) takes the host path with one line of notice.
 
-Not covered: single-member gzip on the device, ``.csi`` / ``.tbi`` random access, BGZF output from the VCF
-writer, a rank reading only its shard's sample columns, multi-allelic splitting (any allele number > 0 is
+Not covered: single-member gzip on the device, ``.csi`` / ``.tbi`` random access and index output (BGZF
+output is ``write_vcf_device(bgzf=True)`` / ``--vcf_bgzf``), a rank reading only its shard's sample columns, multi-allelic splitting (any allele number > 0 is
 ALT), REF / ALT / ID strings, h5 files.
 """
 

@@ -63,6 +63,9 @@ def parse_args(argv=None):
     p.add_argument("--vcf_writer", default="host", choices=["host", "device"],
                    help="host: the Python writer; device: the records formatted on the GPU (vcf_device.py), the same "
                         "file byte for byte")
+    p.add_argument("--vcf_bgzf", action="store_true",
+                   help="write imputed.vcf.gz (bgzipped: BGZF members and the EOF block) instead of imputed.vcf; with "
+                        "--vcf_writer host through zlib, with --vcf_writer device deflated on the GPU (csrc/deflate.hip)")
     p.add_argument("--panel_codes", default="u8", choices=["u8", "bits"],
                    help="layout of the HBM panel index: one byte per site, or bit-packed (1/8 of the memory, "
                         "identical neighbours)")
@@ -115,11 +118,31 @@ def vcf_cells(h1, h2, gt):
             for s in range(len(h1))]
 
 
-def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None):
+class _BgzfText:
+    """``open(path, "w")`` over ``BgzfWriter``: the same text, encoded the same way, as bgzipped members."""
+
+    def __init__(self, path):
+        import locale
+        from .dataset.bgzf import BgzfWriter
+        self.fh, self.encoding = BgzfWriter(path), locale.getpreferredencoding(False)
+
+    def write(self, s: str) -> int:
+        self.fh.write(s.encode(self.encoding))
+        return len(s)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.fh.close()
+
+
+def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, bgzf=False):
     """VCF 4.2 records of the imputed sites (utils.py:378-479 layout: FORMAT GT:HDS:GP:DS,
     ID '.', REF/ALT '.' unless given, QUAL 0, FILTER PASS).  ``pos_flag`` selects the sites
-    written (the reference writes only flagged = imputed positions, infer_embedding_rag.py:237)."""
-    with open(path, "w") as f:
+    written (the reference writes only flagged = imputed positions, infer_embedding_rag.py:237).
+    ``bgzf``: the same text as a bgzipped file (BGZF members of 0xff00 bytes, zlib level 6, the EOF block)."""
+    with (_BgzfText(path) if bgzf else open(path, "w")) as f:
         f.write("##fileformat=VCFv4.2\n##source=rag-snvbert_amd\n")
         f.write('##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype (argmax of GP)">\n')
         f.write('##FORMAT=<ID=HDS,Number=2,Type=Float,Description="Haplotype ALT dosages">\n')
@@ -329,16 +352,17 @@ def infer(argv=None):
                         pos=np.asarray(ds.ori_pos))
     if not args.no_vcf:
         samples = [f"S{i}" for i in range(h1.shape[1])]
-        vcf_path, flag = os.path.join(args.output_path, "imputed.vcf"), mask[:, 0].astype(bool)
+        vcf_path = os.path.join(args.output_path, "imputed.vcf.gz" if args.vcf_bgzf else "imputed.vcf")
+        flag = mask[:, 0].astype(bool)
         if args.vcf_writer == "device":
             # in place from the scatter path's device arrays when there are any, else the host arrays
             # (several ranks: the gathered ones) uploaded chunk by chunk
             src = site_dev if site_dev is not None else dict(h1=h1, h2=h2, gt=gt)
             write_vcf_device(vcf_path, args.chrom, ds.ori_pos, src["h1"], src["h2"], src["gt"], samples,
-                             pos_flag=flag, device=dev)
+                             pos_flag=flag, device=dev, bgzf=args.vcf_bgzf)
             src = site_dev = None      # the device result arrays are freed after the write
         else:
-            write_vcf(vcf_path, args.chrom, ds.ori_pos, h1, h2, gt, samples, pos_flag=flag)
+            write_vcf(vcf_path, args.chrom, ds.ori_pos, h1, h2, gt, samples, pos_flag=flag, bgzf=args.vcf_bgzf)
     print(f"imputed {len(ds)} sample-windows in {res['seconds']:.2f}s "
           f"({res['masked_snvs'] / res['seconds']:.0f} masked SNVs/s)", flush=True)
     return res

@@ -910,6 +910,55 @@ def text_last_newline(text: torch.Tensor, nbytes: int, out: Optional[torch.Tenso
     return out
 
 
+BGZF_SLOT = 65536                    # bytes between two members of ``bgzf_deflate``
+
+
+def bgzf_deflate(text: torch.Tensor, nbytes: int, block_size: int = 0xff00, members: Optional[torch.Tensor] = None,
+                 member_len: Optional[torch.Tensor] = None):
+    """``text[:nbytes]`` (device u8, any alignment) cut into pieces of ``block_size`` bytes, each deflated into
+    one BGZF member: returns (members u8 [n_blocks, 65536], member_len i32 [n_blocks]) on the device; member b
+    is ``members[b, :member_len[b]]`` and the rest of its slot is not touched."""
+    N.require_gpu(text)
+    assert text.dtype == torch.uint8 and text.dim() == 1 and text.is_contiguous()
+    if not 0 <= nbytes <= text.numel() or nbytes >= 1 << 31:
+        raise ValueError(f"bgzf_deflate: nbytes {nbytes} must lie in [0, min(text bytes, 2^31))")
+    if not 1 <= block_size <= 0xff00:
+        raise ValueError(f"bgzf_deflate: block_size {block_size} must lie in [1, 0xff00]")
+    n = -(-nbytes // block_size)
+    dev = text.device
+    if members is None:
+        members = torch.empty(n, BGZF_SLOT, device=dev, dtype=torch.uint8)
+    if member_len is None:
+        member_len = torch.empty(n, device=dev, dtype=torch.int32)
+    assert members.dtype == torch.uint8 and members.is_contiguous() and members.numel() >= n * BGZF_SLOT
+    assert member_len.dtype == torch.int32 and member_len.is_contiguous() and member_len.numel() >= n
+    if members.data_ptr() % 16:
+        raise ValueError("bgzf_deflate: members must be 16-byte aligned")
+    if n:
+        check(N.lib().snvrag_bgzf_deflate(ptr(text), nbytes, block_size, ptr(members), ptr(member_len), stream_ptr()),
+              "bgzf_deflate")
+    return members.view(-1)[:n * BGZF_SLOT].view(n, BGZF_SLOT), member_len[:n]
+
+
+def bgzf_pack(members: torch.Tensor, member_len: torch.Tensor, out: torch.Tensor,
+              total: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The members of ``bgzf_deflate`` copied back to back into ``out`` (device u8); returns total i64 [1] on the
+    device: the bytes written, or -1 (and nothing written) where they do not fit ``out``."""
+    N.require_gpu(members, member_len, out)
+    assert members.dtype == torch.uint8 and members.is_contiguous() and out.dtype == torch.uint8 and out.is_contiguous()
+    assert member_len.dtype == torch.int32 and member_len.dim() == 1 and member_len.is_contiguous()
+    n = member_len.numel()
+    assert members.numel() >= n * BGZF_SLOT
+    if members.data_ptr() % 16:
+        raise ValueError("bgzf_pack: members must be 16-byte aligned")
+    if total is None:
+        total = torch.empty(1, device=out.device, dtype=torch.int64)
+    assert total.dtype == torch.int64 and total.numel() >= 1 and total.data_ptr() % 8 == 0
+    check(N.lib().snvrag_bgzf_pack(ptr(members), ptr(member_len), n, ptr(out), out.numel(), ptr(total), stream_ptr()),
+          "bgzf_pack")
+    return total
+
+
 def ln_fwd_train(x: torch.Tensor, r: Optional[torch.Tensor], g: torch.Tensor, b: torch.Tensor, eps: float,
                  p_r: float = 0.0, p_out: float = 0.0, seed: int = 0, slope_x: float = 0.0, slope_r: float = 0.0):
     """(y bf16, s bf16 = act_x(x) + drop(act_r(r)) (x itself when r is None), stats f32 [M, 2]); y

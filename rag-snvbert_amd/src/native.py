@@ -174,6 +174,8 @@ _SIGS = {
     "snvrag_vcf_unpack_gt": ([vp, vp, i64, i64, i64, vp, vp], C.c_int),
     "snvrag_bgzf_inflate": ([vp, i64, vp, vp, i64, vp, i64, vp, vp], C.c_int),
     "snvrag_text_last_newline": ([vp, i64, vp, vp], C.c_int),
+    "snvrag_bgzf_deflate": ([vp, i64, i64, vp, vp, vp], C.c_int),
+    "snvrag_bgzf_pack": ([vp, vp, i64, vp, i64, vp, vp], C.c_int),
     "snvrag_mlp_pack_bytes": ([C.c_int], sz),
     "snvrag_mlp_pack": ([C.c_int, vp, vp, vp, vp], C.c_int),
     "snvrag_mlp_forward": ([i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, f32, vp, vp], C.c_int),

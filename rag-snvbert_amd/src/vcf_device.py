@@ -26,6 +26,7 @@ import torch
 CELL_BYTES = 40                     # "G:h1,h2:gp0,gp1,gp2:ds" = 39 bytes, plus the tab or newline
 MAX_CHUNK_BYTES = 1 << 30
 DEFAULT_CHUNK_BYTES = 256 << 20
+BGZF_BLOCK = 0xff00                 # text bytes per BGZF member of write_vcf_device(bgzf=True)
 
 
 def milli_f32(values) -> np.ndarray:
@@ -105,8 +106,14 @@ def _host(a):
 
 
 def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, device=None,
-                     chunk_bytes: int = DEFAULT_CHUNK_BYTES) -> bool:
+                     chunk_bytes: int = DEFAULT_CHUNK_BYTES, bgzf: bool = False) -> bool:
     """``write_vcf`` with the records formatted on ``device``: the same file, byte for byte.
+
+    ``bgzf``: the file is bgzipped.  Each chunk's text is deflated into BGZF members of 0xff00 bytes and packed
+    on the device behind the format kernel (csrc/deflate.hip); its byte total is read with the chunk's count of
+    bad values, and only that many bytes cross to the host and reach the file.  Chunks are independent (a
+    chunk's last member is short); the header is written as host-made members and the file ends with the EOF
+    block.  It inflates to the plain file byte for byte; the fallback below then writes a bgzipped file too.
 
     h1 / h2 [n, S] and gt [n, S, 4] are float32 numpy arrays, host tensors or device tensors.  Device
     tensors are formatted in place; host arrays are uploaded one chunk of selected rows at a time.
@@ -133,8 +140,13 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     rows, blob, prefix_off = site_prefixes(chrom, pos, flag, ref, alt)
     length = line_lengths(prefix_off, S)
     chunks = plan_chunks(length, chunk_bytes)
-    with open(path, "w") as f:
-        f.write(header_lines(samples))
+    if bgzf:
+        from .dataset.bgzf import EOF_BLOCK, write_bgzf
+        with open(path, "wb") as f:
+            write_bgzf(f, header_lines(samples).encode(locale.getpreferredencoding(False)), eof=not chunks)
+    else:
+        with open(path, "w") as f:
+            f.write(header_lines(samples))
     if not chunks:
         return True
 
@@ -143,10 +155,19 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     with torch.cuda.device(dev):
         main, side = torch.cuda.current_stream(), torch.cuda.Stream()
         text = [torch.empty(cap + 16, device=dev, dtype=torch.uint8) for _ in range(2)]
-        pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        slots = -(-cap // BGZF_BLOCK)                  # members per chunk, at most; each at most BGZF_BLOCK + 31 bytes
+        pinned = [torch.empty(slots * (BGZF_BLOCK + 31) if bgzf else cap, dtype=torch.uint8).pin_memory()
+                  for _ in range(2)]
         bad = torch.zeros(2, device=dev, dtype=torch.int32)
         bad_host = torch.zeros(2, dtype=torch.int32).pin_memory()
         copied = [torch.cuda.Event(), torch.cuda.Event()]
+        if bgzf:
+            members = [torch.empty(slots, K.BGZF_SLOT, device=dev, dtype=torch.uint8) for _ in range(2)]
+            member_len = [torch.empty(slots, device=dev, dtype=torch.int32) for _ in range(2)]
+            packed = [torch.empty(slots * (BGZF_BLOCK + 31), device=dev, dtype=torch.uint8) for _ in range(2)]
+            small = torch.zeros(2, 4, device=dev, dtype=torch.int32)     # per buffer: bad count, -, total (i64)
+            small_host = torch.zeros(2, 4, dtype=torch.int32).pin_memory()
+            counted, totals = [torch.cuda.Event(), torch.cuda.Event()], [0, 0]
         ok = True
         with open(path, "ab") as f:
 
@@ -154,10 +175,26 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
                 """Chunk c has left the device: its count first, then its bytes to the file."""
                 b = c & 1
                 copied[b].synchronize()
+                if bgzf:                               # start_copy saw its count
+                    f.write(memoryview(pinned[b].numpy())[:totals[b]])
+                    return True
                 if int(bad_host[b]) != 0:
                     return False
                 lo, hi = chunks[c]
                 f.write(memoryview(pinned[b].numpy())[:int(length[lo:hi].sum())])
+                return True
+
+            def start_copy(c):
+                """bgzf: chunk c's count and byte total have arrived; its members follow, that many bytes."""
+                b = c & 1
+                counted[b].synchronize()
+                if int(small_host[b, 0]) != 0:
+                    return False
+                totals[b] = int(small_host[b, 2:4].view(torch.int64))
+                assert 0 <= totals[b] <= packed[b].numel(), "the members of a chunk exceed their bound"
+                with torch.cuda.stream(side):
+                    pinned[b][:totals[b]].copy_(packed[b][:totals[b]], non_blocking=True)
+                    copied[b].record(side)
                 return True
 
             for c, (lo, hi) in enumerate(chunks):
@@ -173,19 +210,32 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
                     a1, a2, ag = (torch.from_numpy(np.ascontiguousarray(a[sel])).to(dev) for a in (h1, h2, gt))
                     r = np.arange(hi - lo, dtype=np.int32)
                 up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-                bad[b:b + 1].zero_()
+                count = small[b, 0:1] if bgzf else bad[b:b + 1]
+                count.zero_()
                 # text[b] / pinned[b] last held chunk c - 2, which finish() saw copied and wrote out
-                K.vcf_format(a1, a2, ag, up(r), up(line_off), up(p_off), up(p_blob), text[b], nbytes, bad[b:b + 1])
+                K.vcf_format(a1, a2, ag, up(r), up(line_off), up(p_off), up(p_blob), text[b], nbytes, count)
+                if bgzf:
+                    mem, mlen = K.bgzf_deflate(text[b], nbytes, BGZF_BLOCK, members[b], member_len[b])
+                    K.bgzf_pack(mem, mlen, packed[b], small[b, 2:4].view(torch.int64))
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    bad_host[b:b + 1].copy_(bad[b:b + 1], non_blocking=True)
-                    pinned[b][:nbytes].copy_(text[b][:nbytes], non_blocking=True)
-                    copied[b].record(side)
+                    if bgzf:
+                        small_host[b].copy_(small[b], non_blocking=True)
+                        counted[b].record(side)
+                    else:
+                        bad_host[b:b + 1].copy_(bad[b:b + 1], non_blocking=True)
+                        pinned[b][:nbytes].copy_(text[b][:nbytes], non_blocking=True)
+                        copied[b].record(side)
                 if c >= 1 and not finish(c - 1):       # overlaps chunk c's format and copy
+                    ok = False
+                    break
+                if bgzf and not start_copy(c):
                     ok = False
                     break
             if ok:
                 ok = finish(len(chunks) - 1)
+            if ok and bgzf:
+                f.write(EOF_BLOCK)
         main.wait_stream(side)                         # the buffers go back to the allocator behind the copies
         torch.cuda.synchronize(dev)
     if ok:
@@ -193,5 +243,5 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     os.remove(path)
     print("write_vcf_device: a value does not fit the fixed-width cell (NaN, infinite, negative or >= 9.9995); "
           "the host writer writes the file", flush=True)
-    write_vcf(path, chrom, pos, _host(h1), _host(h2), _host(gt), samples, pos_flag=flag, ref=ref, alt=alt)
+    write_vcf(path, chrom, pos, _host(h1), _host(h2), _host(gt), samples, pos_flag=flag, ref=ref, alt=alt, bgzf=bgzf)
     return False
