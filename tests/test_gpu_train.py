@@ -210,7 +210,8 @@ def test_linear_dw_kernel_vs_fp32(M, N, K_, splits):
 def test_layernorm_fused_dropout_vs_torch(p_r, p_out):
     """drop_o(LN(x + drop_r(r))) with the masks fused into the LN kernels (csrc/train.hip) ==
     torch on the same masks (tests/attn_helpers.py restates the hash): output, dx, dr, dg, db;
-    with direct_weight_grads the LN parameter gradients land in their .grad buffers (added)."""
+    with direct_weight_grads the LN parameter gradients land in their .grad buffers (added).
+    Kernel-level coverage (fp64 references, per-element bounds, every chunk edge): test_gpu_layernorm_train.py."""
     from attn_helpers import ln_keep_mask
     from src import autograd_ops as A
     from src import kernels as K
@@ -249,6 +250,8 @@ def test_layernorm_fused_dropout_vs_torch(p_r, p_out):
 
 @pytest.mark.parametrize("M,N,resid", [(1000, 384, True), (517, 1536, False), (64, 64, True)])
 def test_hip_add_layernorm_fwd_bwd(M, N, resid):
+    """The autograd wrapper against torch f32 autograd, whole-tensor norm ratios.
+    Kernel-level coverage (fp64 references, per-element bounds, every chunk edge): test_gpu_layernorm_train.py."""
     from src.autograd_ops import hip_add_layernorm
     g = torch.Generator(device="cpu").manual_seed(N)
     ln = torch.nn.LayerNorm(N).to(DEV)
@@ -280,7 +283,8 @@ def test_hip_add_layernorm_fused_leaky_relu(M, N, mode):
     y = LN(lrelu(x)) (the FFN norm on w_1's pre-activation output); r: y = LN(x + lrelu(r)) (the
     output sublayer on w_2's pre-activation output); r_drop: the same with residual dropout
     (checked against the un-fused kernel path on identical masks: same seed).  Forward and every
-    gradient vs torch f32 autograd on the same bf16 inputs, 1e-2 relative (bf16 outputs)."""
+    gradient vs torch f32 autograd on the same bf16 inputs, 1e-2 relative (bf16 outputs).
+    Kernel-level coverage (fp64 references, per-element bounds, every chunk edge): test_gpu_layernorm_train.py."""
     from src.autograd_ops import hip_add_layernorm
     import src.autograd_ops as A
     g = torch.Generator(device="cpu").manual_seed(N + M)
