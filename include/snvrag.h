@@ -741,6 +741,29 @@ int snvrag_vcf_format(int64_t n, int64_t S, const float* h1, const float* h2, co
                       const uint8_t* prefix_blob, int64_t prefix_bytes, uint8_t* out, int64_t out_bytes,
                       int32_t* bad_count, void* stream);
 
+/* Per-site statistics of the same site-major result arrays (opt-in: --vcf_info, --truth_vcf; csrc/quality.hip;
+ * src/quality.py site_stats_host is the specification).  Per sample, in f32 as the writer above: gp1 = gt[1] +
+ * gt[2], ds = gp1 + 2 gt[3]; then in f64 e = ds, f = gp1 + 4 gt[3].
+ *   est    f64 [n][5]: sum h1 + h2, sum h1^2 + h2^2, sum e, sum e^2, sum f over the S samples of the site;
+ *   truth  i8 [n_truth][S_truth][2] (what snvrag_vcf_unpack_gt writes: 0 / 1, -1 missing), or NULL: est only
+ *          (acc, table, truth_row, truth_col and bad_count may then be NULL);
+ *   truth_row i32 [n]: the truth row of each site, -1 none;  truth_col i32 [S]: the truth column of each
+ *          sample, -1 none;
+ *   table  i32 [n][9]: table[3 t + c] += 1 over the samples with a truth column and both truth alleles called,
+ *          t = true ALT count, c = ALT count of the called genotype (0, 1, 1, 2 of the writer's G: the scan
+ *          best = gt[0], k wins when gt[k] > best, so the first maximum and never a NaN);
+ *   acc    f64 [n][3]: sum e, sum e^2, sum e t over the same samples.  A site without a truth row gets zeros.
+ * A truth_row outside [-1, n_truth) or a truth_col outside [-1, S_truth) is treated as -1, loads nothing and
+ * adds 1 to *bad_count (device i32, zeroed by the caller): a row once, a column once (by site 0).
+ * No float atomics: every sum has an order fixed by S alone (two launches give the same bits); every product
+ * is of f32 values and exact in f64.  All pointers are device pointers.
+ * Refused: a null h1 / h2 / gt / est, n < 1, S < 1, n or S >= 2^31, a misaligned gt (16 bytes), truth without
+ * truth_row, truth_col, acc, table and bad_count, n_truth or S_truth outside [1, 2^31). */
+int snvrag_site_stats(int64_t n, int64_t S, const float* h1, const float* h2, const float* gt,
+                      const int8_t* truth, int64_t n_truth, int64_t S_truth, const int32_t* truth_row,
+                      const int32_t* truth_col, double* est, double* acc, int32_t* table, int32_t* bad_count,
+                      void* stream);
+
 /* Device VCF reader (src/dataset/vcf_reader.py; what allel.read_vcf(fields=['variants/POS', 'calldata/GT'])
  * gives the reference, embedding_rag_dataset.py:463-484, embedding_rag_infer_dataset.py:56-69): the body of a
  * VCF parsed on the GPU into the bit rows of snvrag_feature_tables_t.gt_bits and of the packed panel index.

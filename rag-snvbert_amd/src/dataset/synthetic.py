@@ -213,7 +213,7 @@ def make_infer_arrays(n_sites: int = 1300, n_samples: int = 3, n_ref_samples: in
     return dict(ori_pos=ori_pos, pos=ori_pos[keep], vcf=full[keep], freq=freq,
                 pops=[POPS[i % 5] for i in range(n_samples)], pop_to_idx={p: i for i, p in enumerate(POPS)},
                 pos_to_idx={int(p): i for i, p in enumerate(ori_pos)}, ref_gt=panel[ref_rows],
-                ref_pos=ori_pos[ref_rows], source=src)
+                ref_pos=ori_pos[ref_rows], source=src, truth=full)
 
 
 def make_infer_dataset(a: dict = None, index_window_len: int = 510, panel_codes: str = "u8", **kw):

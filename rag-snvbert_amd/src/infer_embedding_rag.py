@@ -66,6 +66,14 @@ def parse_args(argv=None):
     p.add_argument("--vcf_bgzf", action="store_true",
                    help="write imputed.vcf.gz (bgzipped: BGZF members and the EOF block) instead of imputed.vcf; with "
                         "--vcf_writer host through zlib, with --vcf_writer device deflated on the GPU (csrc/deflate.hip)")
+    p.add_argument("--vcf_info", action="store_true",
+                   help="write AF, DR2, R2 and the IMP flag into the INFO column of imputed.vcf (per-site sums on the "
+                        "GPU, csrc/quality.hip; quality.py); off: INFO stays '.'")
+    p.add_argument("--truth_vcf", type=str, default=None,
+                   help="a .vcf / .vcf.gz with the true genotypes: the imputed sites it holds are scored against it "
+                        "(dosage r2, concordance, non-reference concordance by MAF bin) into quality.npz and accuracy.tsv")
+    p.add_argument("--maf_bins", type=str, default=None,
+                   help="MAF bin edges of accuracy.tsv, comma separated (default 0,0.001,0.005,0.01,0.05,0.1,0.2,0.5)")
     p.add_argument("--panel_codes", default="u8", choices=["u8", "bits"],
                    help="layout of the HBM panel index: one byte per site, or bit-packed (1/8 of the memory, "
                         "identical neighbours)")
@@ -137,13 +145,20 @@ class _BgzfText:
         self.fh.close()
 
 
-def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, bgzf=False):
+def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, bgzf=False, info=None):
     """VCF 4.2 records of the imputed sites (utils.py:378-479 layout: FORMAT GT:HDS:GP:DS,
     ID '.', REF/ALT '.' unless given, QUAL 0, FILTER PASS).  ``pos_flag`` selects the sites
     written (the reference writes only flagged = imputed positions, infer_embedding_rag.py:237).
-    ``bgzf``: the same text as a bgzipped file (BGZF members of 0xff00 bytes, zlib level 6, the EOF block)."""
+    ``bgzf``: the same text as a bgzipped file (BGZF members of 0xff00 bytes, zlib level 6, the EOF block).
+    ``info``: one INFO string per site row (``quality.info_strings``: AF, DR2, R2, IMP) in place of '.', and the
+    four ##INFO header lines that declare them."""
+    if info is not None and len(info) != len(pos):
+        raise ValueError("info must hold one string per site row")
     with (_BgzfText(path) if bgzf else open(path, "w")) as f:
         f.write("##fileformat=VCFv4.2\n##source=rag-snvbert_amd\n")
+        if info is not None:
+            from .vcf_device import INFO_HEADER
+            f.write(INFO_HEADER)
         f.write('##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype (argmax of GP)">\n')
         f.write('##FORMAT=<ID=HDS,Number=2,Type=Float,Description="Haplotype ALT dosages">\n')
         f.write('##FORMAT=<ID=GP,Number=3,Type=Float,Description="Genotype probabilities">\n')
@@ -154,7 +169,8 @@ def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, al
                 continue
             r = ref[i] if ref is not None else "."
             a = alt[i] if alt is not None else "."
-            f.write(f"{chrom}\t{int(pos[i])}\t.\t{r}\t{a}\t0.0\tPASS\t.\tGT:HDS:GP:DS\t" +
+            inf = info[i] if info is not None else "."
+            f.write(f"{chrom}\t{int(pos[i])}\t.\t{r}\t{a}\t0.0\tPASS\t{inf}\tGT:HDS:GP:DS\t" +
                     "\t".join(vcf_cells(h1[i], h2[i], gt[i])) + "\n")
 
 
@@ -306,6 +322,47 @@ def _empty_rows(key, dev, k):
     return torch.zeros(shape, device=dev, dtype=dt)
 
 
+def site_quality(args, ds, dev, src, flag):
+    """``--vcf_info`` / ``--truth_vcf`` on rank 0: the per-site sums of ``src`` (h1 / h2 / gt, device tensors or
+    host arrays) by the kernel (quality.py).  Returns the INFO strings for the writers (None without
+    ``--vcf_info``); with ``--truth_vcf`` also writes quality.npz and accuracy.tsv and prints the ALL row.  The
+    imputed sites (``flag``, what the VCF writer selects) that the truth file holds are the ones evaluated."""
+    from . import kernels as K
+    from . import quality as Q
+    S = src["h1"].shape[1]
+    ori_pos = np.asarray(ds.ori_pos)
+    truth = row = col = None
+    if args.truth_vcf:
+        from .dataset.vcf_reader import read_vcf
+        tv = read_vcf(args.truth_vcf, dev)
+        vg = getattr(ds, "vcf_genotypes", None)
+        row, col = Q.truth_maps(tv, ori_pos, None if vg is None else list(vg.samples), n_samples=S)
+        row = np.where(flag, row, -1).astype(np.int32)
+        if tv.n_sites and (row >= 0).any():
+            truth = K.vcf_unpack_gt(tv.alt_bits, tv.miss_bits, tv.n_sites)      # device i8, no host round trip
+    est, acc, table = Q.site_stats(src["h1"], src["h2"], src["gt"], truth, row, col, device=dev)
+    af, r2, dr2 = Q.estimates(est, S)
+    if args.truth_vcf:
+        if truth is None:
+            acc, table = np.zeros((len(ori_pos), 3)), np.zeros((len(ori_pos), 9), np.int32)
+        cols = np.asarray(getattr(ds, "_freq_col", np.arange(len(ori_pos))))
+        gaf = np.asarray(ds.freq[3][5], np.float64)[cols]
+        maf = np.minimum(gaf, 1 - gaf)
+        site = Q.accuracy(acc, table)
+        sel = row >= 0
+        rows = Q.aggregate(acc[sel], table[sel], maf[sel], Q.parse_maf_bins(args.maf_bins))
+        np.savez_compressed(os.path.join(args.output_path, "quality.npz"), pos=ori_pos, flag=flag, est=est, af=af,
+                            r2=r2, dr2=dr2, acc=acc, table=table, truth_row=row, maf=maf, acc_n=site["n"],
+                            acc_r2=site["r2"], concordance=site["concordance"],
+                            nonref_concordance=site["nonref_concordance"])
+        text = Q.accuracy_tsv(rows)
+        with open(os.path.join(args.output_path, "accuracy.tsv"), "w") as f:
+            f.write(text)
+        print("accuracy vs truth  " + text.splitlines()[0].replace("\t", " "), flush=True)
+        print("accuracy vs truth  " + text.splitlines()[-1].replace("\t", " "), flush=True)
+    return Q.info_strings(af, r2, dr2) if args.vcf_info and not args.no_vcf else None
+
+
 def infer(argv=None):
     args = parse_args(argv)
     from .dataset.vcf_reader import set_default_inflate
@@ -340,9 +397,10 @@ def infer(argv=None):
         model.load_state_dict(sd, strict=True)
     model = model.to(dev).eval()
     engine_for(model).set_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
+    want_quality = bool(args.truth_vcf) or (args.vcf_info and not args.no_vcf)
     res = run(ds, model, dev, args.infer_batch_size, args.k_retrieve, args.num_workers, args.window_len,
               device_features=args.device_features,
-              keep_site_dev=args.vcf_writer == "device" and not args.no_vcf)
+              keep_site_dev=(args.vcf_writer == "device" and not args.no_vcf) or want_quality)
     h1, h2, gt, mask = res["h1"], res["h2"], res["gt"], res["mask"]
     site_dev = res.pop("site_dev", None)
     if rank != 0:                      # the gathered arrays are written once
@@ -350,19 +408,26 @@ def infer(argv=None):
     os.makedirs(args.output_path, exist_ok=True)
     np.savez_compressed(os.path.join(args.output_path, "imputed.npz"), hap1=h1, hap2=h2, gp=gt, mask=mask,
                         pos=np.asarray(ds.ori_pos))
+    flag = mask[:, 0].astype(bool)
+    info = None
+    if want_quality:
+        # in place from the scatter path's device arrays when there are any, else the host arrays through the
+        # chunked upload (several ranks: the gathered ones)
+        info = site_quality(args, ds, dev, site_dev if site_dev is not None else dict(h1=h1, h2=h2, gt=gt), flag)
     if not args.no_vcf:
         samples = [f"S{i}" for i in range(h1.shape[1])]
         vcf_path = os.path.join(args.output_path, "imputed.vcf.gz" if args.vcf_bgzf else "imputed.vcf")
-        flag = mask[:, 0].astype(bool)
         if args.vcf_writer == "device":
             # in place from the scatter path's device arrays when there are any, else the host arrays
             # (several ranks: the gathered ones) uploaded chunk by chunk
             src = site_dev if site_dev is not None else dict(h1=h1, h2=h2, gt=gt)
             write_vcf_device(vcf_path, args.chrom, ds.ori_pos, src["h1"], src["h2"], src["gt"], samples,
-                             pos_flag=flag, device=dev, bgzf=args.vcf_bgzf)
-            src = site_dev = None      # the device result arrays are freed after the write
+                             pos_flag=flag, device=dev, bgzf=args.vcf_bgzf, info=info)
+            src = None
         else:
-            write_vcf(vcf_path, args.chrom, ds.ori_pos, h1, h2, gt, samples, pos_flag=flag, bgzf=args.vcf_bgzf)
+            write_vcf(vcf_path, args.chrom, ds.ori_pos, h1, h2, gt, samples, pos_flag=flag, bgzf=args.vcf_bgzf,
+                      info=info)
+    site_dev = None                    # the device result arrays are freed after the last reader
     print(f"imputed {len(ds)} sample-windows in {res['seconds']:.2f}s "
           f"({res['masked_snvs'] / res['seconds']:.0f} masked SNVs/s)", flush=True)
     return res

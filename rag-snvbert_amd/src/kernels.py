@@ -776,6 +776,41 @@ def vcf_format(h1: torch.Tensor, h2: torch.Tensor, gt: torch.Tensor, rows: torch
                                     ptr(bad_count), stream_ptr()), "vcf_format")
 
 
+def site_stats(h1: torch.Tensor, h2: torch.Tensor, gt: torch.Tensor, truth: Optional[torch.Tensor] = None,
+               truth_row: Optional[torch.Tensor] = None, truth_col: Optional[torch.Tensor] = None,
+               bad_count: Optional[torch.Tensor] = None):
+    """(est f64 [n, 5], acc f64 [n, 3], table i32 [n, 9]) of the site-major result arrays h1 / h2 f32 [n, S],
+    gt f32 [n, S, 4] (``quality.site_stats_host`` is the specification; include/snvrag.h lists the sums).
+    ``truth`` i8 [n_truth, S_truth, 2] with ``truth_row`` i32 [n] and ``truth_col`` i32 [S] (-1: none); without
+    it only ``est`` is computed and acc / table are None.  ``bad_count`` i32 [1] += the indices out of range
+    (allocated and zeroed here when not given; ``quality.site_stats`` reads it)."""
+    N.require_gpu(h1, h2, gt, truth, truth_row, truth_col, bad_count)
+    n, S = h1.shape
+    assert h2.shape == (n, S) and gt.shape == (n, S, 4)
+    assert h1.dtype == h2.dtype == gt.dtype == torch.float32
+    assert h1.is_contiguous() and h2.is_contiguous() and gt.is_contiguous()
+    dev = h1.device
+    est = torch.empty(n, 5, device=dev, dtype=torch.float64)
+    acc = table = None
+    n_truth = S_truth = 0
+    if truth is not None:
+        assert truth_row is not None and truth_col is not None, "truth needs truth_row and truth_col"
+        assert truth.dtype == torch.int8 and truth.dim() == 3 and truth.shape[2] == 2 and truth.is_contiguous()
+        assert truth_row.dtype == truth_col.dtype == torch.int32
+        assert truth_row.is_contiguous() and truth_col.is_contiguous()
+        assert truth_row.numel() == n and truth_col.numel() == S
+        n_truth, S_truth = truth.shape[:2]
+        acc = torch.empty(n, 3, device=dev, dtype=torch.float64)
+        table = torch.empty(n, 9, device=dev, dtype=torch.int32)
+        if bad_count is None:
+            bad_count = torch.zeros(1, device=dev, dtype=torch.int32)
+        assert bad_count.dtype == torch.int32 and bad_count.numel() >= 1
+    check(N.lib().snvrag_site_stats(n, S, ptr(h1), ptr(h2), ptr(gt), ptr(truth), n_truth, S_truth, ptr(truth_row),
+                                    ptr(truth_col), ptr(est), ptr(acc), ptr(table), ptr(bad_count), stream_ptr()),
+          "site_stats")
+    return est, acc, table
+
+
 def _text_ok(text: torch.Tensor, nbytes: int) -> None:
     assert text.dtype == torch.uint8 and text.dim() == 1 and text.is_contiguous()
     assert 1 <= nbytes and (nbytes + 15) // 16 * 16 <= text.numel(), "the text buffer must hold the '\\n' padding"

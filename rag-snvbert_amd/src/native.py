@@ -165,6 +165,7 @@ _SIGS = {
     "snvrag_batch_features": ([C.POINTER(FeatureTables), vp, vp, i64, i32, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_int, C.c_int, vp, vp, vp, vp, vp], C.c_int),
     "snvrag_vcf_format": ([i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp], C.c_int),
+    "snvrag_site_stats": ([i64, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp], C.c_int),
     "snvrag_vcf_line_index_ws_bytes": ([i64], sz),
     "snvrag_vcf_line_index": ([vp, i64, i64, vp, vp, vp, sz, vp], C.c_int),
     "snvrag_vcf_parse_ws_bytes": ([i64, i64], sz),

@@ -49,9 +49,17 @@ def milli_f32(values) -> np.ndarray:
     return np.where(bad | (q > 9999), -1, q).astype(np.int64)
 
 
-def header_lines(samples) -> str:
-    """The header ``write_vcf`` writes (same expressions)."""
-    return ("##fileformat=VCFv4.2\n##source=rag-snvbert_amd\n"
+INFO_HEADER = ('##INFO=<ID=AF,Number=1,Type=Float,Description="Estimated ALT allele frequency (mean haplotype dosage)">\n'
+               '##INFO=<ID=DR2,Number=1,Type=Float,Description="Dosage r2 estimated from the genotype probabilities '
+               '(Beagle-style)">\n'
+               '##INFO=<ID=R2,Number=1,Type=Float,Description="Haplotype-dosage variance over its binomial expectation '
+               '(Minimac-style)">\n'
+               '##INFO=<ID=IMP,Number=0,Type=Flag,Description="Imputed site">\n')
+
+
+def header_lines(samples, info: bool = False) -> str:
+    """The header ``write_vcf`` writes (same expressions); ``info``: with the four ##INFO lines of ``info=``."""
+    return ("##fileformat=VCFv4.2\n##source=rag-snvbert_amd\n" + (INFO_HEADER if info else "") +
             '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype (argmax of GP)">\n'
             '##FORMAT=<ID=HDS,Number=2,Type=Float,Description="Haplotype ALT dosages">\n'
             '##FORMAT=<ID=GP,Number=3,Type=Float,Description="Genotype probabilities">\n'
@@ -59,10 +67,11 @@ def header_lines(samples) -> str:
             "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join(samples) + "\n")
 
 
-def site_prefixes(chrom, pos, pos_flag=None, ref=None, alt=None, encoding=None):
+def site_prefixes(chrom, pos, pos_flag=None, ref=None, alt=None, encoding=None, info=None):
     """(rows int32 [n_lines], blob bytes, prefix_off int32 [n_lines + 1]): the selected site rows
     (``pos_flag`` as ``write_vcf`` reads it) and their line prefixes — everything ``write_vcf`` puts in
-    front of the first cell, the tab included — concatenated."""
+    front of the first cell, the tab included — concatenated.  ``info``: the INFO string of every site row
+    (``write_vcf(info=...)``), '.' without it."""
     encoding = encoding or locale.getpreferredencoding(False)      # what open(path, "w") encodes with
     rows, parts, off = [], [], [0]
     for i in range(len(pos)):
@@ -70,7 +79,8 @@ def site_prefixes(chrom, pos, pos_flag=None, ref=None, alt=None, encoding=None):
             continue
         r = ref[i] if ref is not None else "."
         a = alt[i] if alt is not None else "."
-        b = f"{chrom}\t{int(pos[i])}\t.\t{r}\t{a}\t0.0\tPASS\t.\tGT:HDS:GP:DS\t".encode(encoding)
+        inf = info[i] if info is not None else "."
+        b = f"{chrom}\t{int(pos[i])}\t.\t{r}\t{a}\t0.0\tPASS\t{inf}\tGT:HDS:GP:DS\t".encode(encoding)
         rows.append(i)
         parts.append(b)
         off.append(off[-1] + len(b))
@@ -106,7 +116,7 @@ def _host(a):
 
 
 def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, device=None,
-                     chunk_bytes: int = DEFAULT_CHUNK_BYTES, bgzf: bool = False) -> bool:
+                     chunk_bytes: int = DEFAULT_CHUNK_BYTES, bgzf: bool = False, info=None) -> bool:
     """``write_vcf`` with the records formatted on ``device``: the same file, byte for byte.
 
     ``bgzf``: the file is bgzipped.  Each chunk's text is deflated into BGZF members of 0xff00 bytes and packed
@@ -114,6 +124,9 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     bad values, and only that many bytes cross to the host and reach the file.  Chunks are independent (a
     chunk's last member is short); the header is written as host-made members and the file ends with the EOF
     block.  It inflates to the plain file byte for byte; the fallback below then writes a bgzipped file too.
+
+    ``info``: one INFO string per site row, as ``write_vcf(info=...)``: it takes the place of '.' in the line
+    prefixes (host-built, of any width) and adds the four ##INFO header lines.
 
     h1 / h2 [n, S] and gt [n, S, 4] are float32 numpy arrays, host tensors or device tensors.  Device
     tensors are formatted in place; host arrays are uploaded one chunk of selected rows at a time.
@@ -136,17 +149,20 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     n, S = h1.shape
     if h2.shape != (n, S) or gt.shape != (n, S, 4) or len(samples) != S or len(pos) != n:
         raise ValueError("h1 / h2 [n, S], gt [n, S, 4], pos [n] and samples [S] do not agree")
+    if info is not None and len(info) != n:
+        raise ValueError("info must hold one string per site row")
     flag = None if pos_flag is None else _host(pos_flag)
-    rows, blob, prefix_off = site_prefixes(chrom, pos, flag, ref, alt)
+    rows, blob, prefix_off = site_prefixes(chrom, pos, flag, ref, alt, info=info)
     length = line_lengths(prefix_off, S)
     chunks = plan_chunks(length, chunk_bytes)
     if bgzf:
         from .dataset.bgzf import EOF_BLOCK, write_bgzf
         with open(path, "wb") as f:
-            write_bgzf(f, header_lines(samples).encode(locale.getpreferredencoding(False)), eof=not chunks)
+            write_bgzf(f, header_lines(samples, info is not None).encode(locale.getpreferredencoding(False)),
+                       eof=not chunks)
     else:
         with open(path, "w") as f:
-            f.write(header_lines(samples))
+            f.write(header_lines(samples, info is not None))
     if not chunks:
         return True
 
@@ -243,5 +259,6 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     os.remove(path)
     print("write_vcf_device: a value does not fit the fixed-width cell (NaN, infinite, negative or >= 9.9995); "
           "the host writer writes the file", flush=True)
-    write_vcf(path, chrom, pos, _host(h1), _host(h2), _host(gt), samples, pos_flag=flag, ref=ref, alt=alt, bgzf=bgzf)
+    write_vcf(path, chrom, pos, _host(h1), _host(h2), _host(gt), samples, pos_flag=flag, ref=ref, alt=alt, bgzf=bgzf,
+              info=info)
     return False
