@@ -27,9 +27,7 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16(int nseq, int L, int H, con
   using C = AttnCfg<DH>;
   __shared__ __attribute__((aligned(16))) char smem[2 * C::STAGE];
 
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int qq = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int wg = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + orig / 8;
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int qb = wg % nqb, sh = wg / nqb, h = sh % H, seq = sh / H;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -215,18 +213,9 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16(int nseq, int L, int H, con
 // wave recomputes its queries with an exact online-max softmax straight from global
 // memory (attn32_online) — correctness never depends on the data range.
 namespace a32 {
+using namespace t32;                               // K tile: the k_off image; V tile: the transposed-readable img
 constexpr int QPW = 32, WAVES = 4, QPB = QPW * WAVES, KT = 64;
-constexpr int TB = KT * 64;                        // one K or V tile: 64 keys x 64 B
-// K tile: 64-B rows, chunk XOR (-(key>>2))&3 — conflict-free for the ds_read_b128 lane groups
-__device__ __forceinline__ int k_off(int key, int chunk) { return key * 64 + ((chunk ^ ((-(key >> 2)) & 3)) << 4); }
-// V tile: 64-B rows, 32-B halves swapped on (key>>2)&1 — conflict-free ds_read_b64_tr_b16
-__device__ __forceinline__ int v_off(int key, int half) { return key * 64 + ((half ^ ((key >> 2) & 1)) << 5); }
-__device__ __forceinline__ bf16x4 tr_read(const char* p) {
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-__device__ __forceinline__ bf16x8 cat(bf16x4 a, bf16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
+constexpr int TB = TILE;                           // one K or V tile: 64 keys x 64 B
 
 struct State {
   f32x4 o[2][2];     // [e][qt]: O^T rows 16e + 4lg + r, query column li
@@ -297,17 +286,13 @@ __device__ __forceinline__ void tile(const char* Kt, const char* Vt, int kbase, 
     }
   }
   constexpr int NCB = (NKT + 1) / 2;
-  const int tq = li >> 2, tp = li & 3;          // ds_read_b64_tr_b16: lane 4q+p -> row q, columns 4p..4p+3
   // VAR 5: the V^T fragments read right after the S MFMAs, their LDS latency under the exps
   bf16x8 vpre[VAR == 5 ? NCB : 1][2];
   if constexpr (VAR == 5) {
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int k0 = 32 * cb + 4 * lg + tq;
-        vpre[cb][e] = cat(tr_read(Vt + v_off(k0, e) + 8 * tp), tr_read(Vt + v_off(k0 + 16, e) + 8 * tp));
-      }
+      for (int e = 0; e < 2; ++e) vpre[cb][e] = tfrag(Vt, e, cb, li, lg);
   }
   bf16x8 pb[NCB][2];
   bf16x8 pd[TRAIN ? NCB : 1][2];                 // TRAIN: the dropped-out PV operand
@@ -351,9 +336,7 @@ __device__ __forceinline__ void tile(const char* Kt, const char* Vt, int kbase, 
   for (int cb = 0; cb < NCB; ++cb) {
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-      const int k0 = 32 * cb + 4 * lg + tq;
-      const bf16x8 vf = VAR == 5 ? vpre[VAR == 5 ? cb : 0][e]
-                                 : cat(tr_read(Vt + v_off(k0, e) + 8 * tp), tr_read(Vt + v_off(k0 + 16, e) + 8 * tp));
+      const bf16x8 vf = VAR == 5 ? vpre[VAR == 5 ? cb : 0][e] : tfrag(Vt, e, cb, li, lg);
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt)
         st.o[e][qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, TRAIN ? pd[TRAIN ? cb : 0][qt] : pb[cb][qt],
@@ -469,12 +452,11 @@ __device__ __forceinline__ void attn32_online(const bf16* Kp, const bf16* Vp, lo
 // addressing) on a loop that is VALU-issue bound (v_exp + cvt + MFMA issue), plus a
 // vmcnt(0) stall when the one-tile-ahead load was not back; here a wave issues 2 LDS-DMA
 // instructions per tile whose per-lane offsets are loop-invariant (the tile advance rides in
-// soffset), the swizzles of k_off / v_off are applied to the SOURCE addresses, loads run 3
+// soffset), the swizzles of the K image (k_off) / V image (img) are applied to the SOURCE addresses, loads run 3
 // tiles ahead, and the full-tile loop is unrolled by the ring depth so every LDS address is an
 // instruction immediate.  Rows past L read the next sequence (finite data; their scores are
 // masked to -inf and their P is 0) or, past the tensor, the buffer's out-of-range zeros.
 namespace a32 {
-constexpr int NS = 4;                           // ring slots
 constexpr int SLOT = 2 * TB;                    // K tile + V tile
 }  // namespace a32
 
@@ -488,9 +470,7 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
                                                   float* __restrict__ lse = nullptr, AttnDrop drop = AttnDrop{}) {
   using namespace a32;
   __shared__ __attribute__((aligned(16))) char smem[NS * SLOT];
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int qq = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  const int wg = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + orig / 8;
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int qb = wg % nqb, sh = wg / nqb, h = sh % H, seq = sh / H;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -518,20 +498,17 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
     }
     qf[qt] = v;
   }
-  // retire the Q loads HERE: the waitcnt pass would otherwise place their wait at the first use,
-  // inside the tile loop (the loop header merges the preheader's pending loads), where it
-  // becomes an s_waitcnt vmcnt(0) per tile that also drains the LDS-DMA ring
-  asm volatile("" : "+v"(qf[0]), "+v"(qf[1]));
+  retire_loads(qf[0], qf[1]);
 
   // K / V pieces: wave w moves keys 16 w .. 16 w + 15 of a tile (1 KiB of K, 1 KiB of V); lane
   // l lands at byte 16 l of the piece, i.e. key 16 w + l / 4, image chunk l % 4, so it loads the
-  // source chunk that k_off / v_off put there
+  // source chunk that the K image (k_off) / the V image (img) put there
   const long rem = (total_rows - (long)seq * L) * ld * 2;
   const i32x4 rs = dma_rsrc(qkv + base, rem);
   const int pw = NW == 8 ? wave & 3 : wave;         // the 16-key piece this wave moves
   const int kk = 16 * pw + (lane >> 2), c4 = lane & 3;
   const int kc = c4 ^ ((-(kk >> 2)) & 3);
-  const int vc = 2 * ((c4 >> 1) ^ ((kk >> 2) & 1)) + (c4 & 1);
+  const int vc = 2 * ((c4 >> 1) ^ ((kk >> 2) & 1)) + (c4 & 1);   // = img_src(kk, c4)
   const int vk = (int)(kk * ld * 2) + (D + h * 32) * 2 + kc * 16;
   const int vv = (int)(kk * ld * 2) + (2 * D + h * 32) * 2 + vc * 16;
   const int tile_bytes = (int)(KT * ld * 2);
@@ -548,13 +525,7 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
       dma_x4(rs, lds_w + slot * SLOT + TB, vv, t * tile_bytes);
     }
   };
-  // retire this wave's pieces of tile t: y = younger tiles still in flight (<= NS - 2)
   constexpr int PPT = NW == 8 ? 1 : 2;              // DMA instructions per wave per tile
-  auto wait = [&](int y) {
-    if (y >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPT) : "memory");
-    else if (y == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPT) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
 
   State st;
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -574,7 +545,7 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
   // t + NS - 1 exists, so the wait and the issue are unconditional)
   auto step = [&](auto s_tag, int t) {
     constexpr int S = decltype(s_tag)::value;
-    wait(NS - 2);
+    ring_wait<PPT>(NS - 2);
     __builtin_amdgcn_s_barrier();                  // tile t visible; every wave is done with t - 1
     issue(t + NS - 1, (S + NS - 1) % NS);
     // a wave past L (3 of the 4 waves of the last query block at L = 1030: 8 % of all waves) only
@@ -593,7 +564,7 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
     // block of tile t (every wave then is done with V of t - 1 and has landed tile t + 1), the
     // look-ahead drops to 2 tiles (tile t + 3 issued into the slot of t - 1 at that barrier)
     bf16x8 kcur[4];
-    wait(1);
+    ring_wait<PPT>(1);
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) kcur[kt] = *reinterpret_cast<const bf16x8*>(smem + k_off(16 * kt + li, lg));
@@ -601,7 +572,7 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
       constexpr int S = decltype(s_tag)::value;
       bf16x8 knext[4];
       auto mid = [&]() {
-        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");      // this wave's pieces of tile t + 1
+        ring_wait<PPT>(1);                                      // this wave's pieces of tile t + 1
         __builtin_amdgcn_s_barrier();
         issue(t + NS - 1, (S + NS - 1) % NS);
         const char* Kn = smem + ((S + 1) % NS) * SLOT;
@@ -643,7 +614,7 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
   }
   }
   for (; t < ntile; ++t) {                         // the last < NS full tiles and the ragged tail
-    wait(min(NS - 2, ntile - 1 - t));
+    ring_wait<PPT>(min(NS - 2, ntile - 1 - t));
     __builtin_amdgcn_s_barrier();
     if (t + NS - 1 < ntile) issue(t + NS - 1, (t + NS - 1) % NS);
     if (active) {
@@ -678,14 +649,8 @@ __global__ __launch_bounds__(VAR == 4 ? 512 : 256, VAR == 4 || VAR == 5 ? 4 : 1)
     if constexpr (TRAIN) {
       if (lg == 0) lse[((long)seq * H + h) * L + q] = -scale_log2e * st.negm[qt][0] + log2f(st.ls[qt][0]);
     }
-    bf16* op = out + (long)seq * L * ldo + (long)q * ldo + h * 32;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      bf16x4 w;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) w[r] = (bf16)(st.o[e][qt][r] * inv);
-      *reinterpret_cast<bf16x4*>(op + 16 * e + 4 * lg) = w;
-    }
+    const f32x4 oq[2] = {st.o[0][qt], st.o[1][qt]};
+    store_acc_bf16(out + (long)seq * L * ldo + (long)q * ldo + h * 32, oq, inv, lg);
   }
 }
 
@@ -796,8 +761,8 @@ extern "C" int snvrag_attention_fallbacks(int reset) {
   return v;
 }
 
-// Training forward: the generic bf16 kernel (online softmax) plus the per-row log2-sum-exp
-// the backward (attention_train.hip) rebuilds P from.
+// Training forward: attn32_dma<false, true> at head dim 32, the generic bf16 kernel (online
+// softmax) at 64, plus the per-row log2-sum-exp the backward (attention_train.hip) rebuilds P from.
 extern "C" int snvrag_attention_train_fwd(int64_t nseq, int64_t L, int heads, int dh, const void* qkv,
                                           int64_t ld_qkv, void* out, int64_t ld_out, float* lse, float scale,
                                           float dropout_p, uint64_t seed, void* stream) {

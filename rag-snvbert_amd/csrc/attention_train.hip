@@ -2,7 +2,8 @@
 //
 // Reference: model/attention/attention.py:21-31 (softmax(Q K^T / sqrt(dh)) V, no mask)
 // under autograd, with the head split/merge of multi_head_attention.py:44-51.  The
-// forward (attention.hip attn_fwd_bf16 with an lse pointer) stores
+// forward (attention.hip: attn32_dma<false, true> at head dim 32, attn_fwd_bf16 with an lse
+// pointer at 64) stores
 // lse[q] = log2 sum_k exp2(c s_qk), c = scale * log2(e); with P = exp2(c S - lse):
 //   D_q  = sum_d dO[q,d] O[q,d]
 //   dS   = P o (dO V^T - D)            (gradient w.r.t. the scaled scores)
@@ -26,81 +27,6 @@
 
 namespace snvrag {
 
-template <int DH>
-struct BwdCfg {
-  using C = AttnCfg<DH>;
-  static constexpr int CH = C::CPR;                         // 16-B chunks per row
-  static constexpr int NLD = (64 * CH + 255) / 256;         // loads per thread per 64-row tile
-};
-
-// XCD-aware block order (consecutive tiles of one (sequence, head) share an XCD's L2)
-__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
-  const int qq = nwg / 8, rr = nwg % 8, xcd = orig % 8;
-  return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + orig / 8;
-}
-
-// load a 64-row x DH bf16 tile (rows >= L are zero) into registers
-template <int DH>
-__device__ __forceinline__ void tile_load(u32x4 (&r)[BwdCfg<DH>::NLD], const bf16* __restrict__ P, long ld, int t0,
-                                          int L, int tid) {
-  using B = BwdCfg<DH>;
-#pragma unroll
-  for (int i = 0; i < B::NLD; ++i) {
-    const int id = tid + 256 * i;
-    const int row = id / B::CH, c = id % B::CH;
-    const int rr = t0 + row, d0 = 8 * c;
-    if (id < 64 * B::CH && rr < L && d0 < DH) r[i] = *reinterpret_cast<const u32x4*>(P + (long)rr * ld + d0);
-    else r[i] = u32x4{0u, 0u, 0u, 0u};
-  }
-}
-// row-major swizzled store (A operand rows: MFMA reads row li, chunk 4 ks + lg)
-template <int DH>
-__device__ __forceinline__ void tile_store_rows(char* dst, const u32x4 (&r)[BwdCfg<DH>::NLD], int tid) {
-  using B = BwdCfg<DH>;
-#pragma unroll
-  for (int i = 0; i < B::NLD; ++i) {
-    const int id = tid + 256 * i;
-    if (id < 64 * B::CH) *reinterpret_cast<u32x4*>(dst + k_off<DH>(id / B::CH, id % B::CH)) = r[i];
-  }
-}
-// transposed store [d][row] with row stride VT_LD (A operand of the P / dS products)
-template <int DH>
-__device__ __forceinline__ void tile_store_t(char* dst, const u32x4 (&r)[BwdCfg<DH>::NLD], int tid) {
-  using B = BwdCfg<DH>;
-  using C = AttnCfg<DH>;
-  bf16* t = reinterpret_cast<bf16*>(dst);
-#pragma unroll
-  for (int i = 0; i < B::NLD; ++i) {
-    const int id = tid + 256 * i;
-    if (id < 64 * B::CH) {
-      const int row = id / B::CH, c = id % B::CH;
-      const bf16x8 v = __builtin_bit_cast(bf16x8, r[i]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) t[(8 * c + j) * C::VT_LD + row] = v[j];
-    }
-  }
-}
-// A fragment of a transposed tile whose k = 64 rows follow the accumulator order of a
-// 4 x (16-row) score block: half c covers rows 32c + 4 lg + {0..3} and 32c + 16 + 4 lg + {0..3}
-template <int DH>
-__device__ __forceinline__ bf16x8 t_frag(const char* tt, int e, int c, int li, int lg) {
-  using C = AttnCfg<DH>;
-  const bf16* row = reinterpret_cast<const bf16*>(tt) + (16 * e + li) * C::VT_LD + 32 * c + 4 * lg;
-  const bf16x4 lo = *reinterpret_cast<const bf16x4*>(row);
-  const bf16x4 hi = *reinterpret_cast<const bf16x4*>(row + 16);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-// B fragment of this lane's row r over d: k = 32 ks + 8 lg + j
-template <int DH>
-__device__ __forceinline__ void row_frag(bf16x8 (&f)[AttnCfg<DH>::KS], const bf16* __restrict__ P, long ld, int r,
-                                         int L, int lg) {
-#pragma unroll
-  for (int ks = 0; ks < AttnCfg<DH>::KS; ++ks) {
-    const int d0 = 32 * ks + 8 * lg;
-    f[ks] = (r < L && d0 < DH) ? *reinterpret_cast<const bf16x8*>(P + (long)r * ld + d0) : bf16x8{};
-  }
-}
-
 // ------------------------------------------------------------------- dQ ---
 template <int DH>
 __global__ __launch_bounds__(256) void attn_bwd_dq(int L, int H, const bf16* __restrict__ qkv, long ld,
@@ -110,7 +36,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(int L, int H, const bf16* __r
                                                    bf16* __restrict__ dqkv, long ldd, float c_log2e, float scale,
                                                    int nqb, AttnDrop drop) {
   using C = AttnCfg<DH>;
-  using B = BwdCfg<DH>;
   constexpr int STAGE = 2 * C::KBYTES + C::VBYTES;          // K rows, V rows, K^T
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
@@ -138,7 +63,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(int L, int H, const bf16* __r
   const uint32_t dbase = drop_base(drop.seed, (uint32_t)sh);
   if (q < L && lg == 0) Dout[srow + q] = dq_;
 
-  u32x4 kr[B::NLD], vr[B::NLD];
+  u32x4 kr[C::NLD], vr[C::NLD];
   auto store = [&](char* st) {
     tile_store_rows<DH>(st, kr, tid);
     tile_store_rows<DH>(st + C::KBYTES, vr, tid);
@@ -175,7 +100,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(int L, int H, const bf16* __r
       }
     }
     bf16x8 dsb[2];
-    // hash input of (q, key pair (64 t + 4 lg) / 2); (kt, r) adds 8 kt + r / 2
     const uint32_t drow = drop_row(dbase, (uint32_t)q, (uint32_t)(32 * t + 2 * lg));
     // straight-line element math (raw v_exp_f32, no per-element branches); only the ragged
     // last key tile masks keys >= L
@@ -185,8 +109,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(int L, int H, const bf16* __r
       for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
-          float dm[2] = {1.f, 1.f};
-          if (drop.thresh) drop_split(drop, drop_mix24(drow + (uint32_t)(8 * kt + (r >> 1)) * DROP_C2), dm[0], dm[1]);
+          float dm[2];
+          drop_mul_dq(drop, drow, kt, r, dm);
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
             float p = __builtin_amdgcn_exp2f(s[kt][r + e] * c_log2e - lse_q);
@@ -208,16 +132,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(int L, int H, const bf16* __r
     if (more) store(smem + ((t + 1) & 1) * STAGE);
     __syncthreads();
   }
-  if (q < L) {
-    bf16* op = dqkv + (row0 + q) * ldd + h * DH;
-#pragma unroll
-    for (int e = 0; e < C::ET; ++e) {
-      bf16x4 w;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) w[r] = (bf16)(acc[e][r] * scale);
-      *reinterpret_cast<bf16x4*>(op + 16 * e + 4 * lg) = w;
-    }
-  }
+  if (q < L) store_acc_bf16(dqkv + (row0 + q) * ldd + h * DH, acc, scale, lg);
 }
 
 // ------------------------------------------------------------------ dKV ---
@@ -228,7 +143,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv(int L, int H, const bf16* __
                                                     bf16* __restrict__ dqkv, long ldd, float c_log2e, float scale,
                                                     int nkb, AttnDrop drop) {
   using C = AttnCfg<DH>;
-  using B = BwdCfg<DH>;
   constexpr int STAGE = 2 * C::KBYTES + 2 * C::VBYTES + 2 * 64 * 4;   // Q, dO rows; Q^T, dO^T; lse, D
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
@@ -246,7 +160,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv(int L, int H, const bf16* __
   row_frag<DH>(kf, qkv + row0 * ld + D + h * DH, ld, key, L, lg);
   row_frag<DH>(vf, qkv + row0 * ld + 2 * D + h * DH, ld, key, L, lg);
 
-  u32x4 qr[B::NLD], gr[B::NLD];
+  u32x4 qr[C::NLD], gr[C::NLD];
   float lr = 0.f, dr = 0.f;
   auto load = [&](int t0) {
     tile_load<DH>(qr, Qp, ld, t0, L, tid);
@@ -293,26 +207,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv(int L, int H, const bf16* __
       }
     }
     bf16x8 pb[2], dsb[2];
-    // dropout multipliers: the keys of a hash pair sit in lanes li, li ^ 1 with the same 16
-    // queries, so each lane hashes half of them (r in {0,1} even lanes, {2,3} odd lanes) and
-    // swaps with its neighbour (DPP quad_perm [1,0,3,2]); it then takes its key's 16-bit half
     float mkv[4][4];
-    if (drop.thresh) {
-      const bool odd = li & 1;
-      // hash input of (query 64 t + 4 lg (+ 2 on odd lanes), this key's pair); (qt, rr) adds
-      // (16 qt + rr) * C1
-      const uint32_t drow = drop_row(dbase, (uint32_t)(t * 64 + 4 * lg + (odd ? 2 : 0)), (uint32_t)key >> 1);
-#pragma unroll
-      for (int qt = 0; qt < 4; ++qt)
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-          const uint32_t hm = drop_mix24(drow + (uint32_t)(16 * qt + rr) * DROP_C1);
-          const uint32_t ho = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hm, 0xB1, 0xF, 0xF, false);
-          const uint32_t h_lo = odd ? ho : hm, h_hi = odd ? hm : ho;       // hashes of r = rr, 2 + rr
-          mkv[qt][rr] = (odd ? h_lo >> 16 : h_lo & 0xFFFFu) >= drop.thresh ? drop.scale : 0.f;
-          mkv[qt][2 + rr] = (odd ? h_hi >> 16 : h_hi & 0xFFFFu) >= drop.thresh ? drop.scale : 0.f;
-        }
-    }
+    drop_mul_dkv(drop, dbase, t, key, li, lg, mkv);
     // straight-line element math (raw v_exp_f32); only the ragged last query tile masks q >= L
     auto elem = [&](auto mask_tag) {
       constexpr bool MASK = decltype(mask_tag)::value;
@@ -345,16 +241,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv(int L, int H, const bf16* __
     __syncthreads();
   }
   if (key < L) {
-    bf16* kp = dqkv + (row0 + key) * ldd + D + h * DH;
-    bf16* vp = dqkv + (row0 + key) * ldd + 2 * D + h * DH;
-#pragma unroll
-    for (int e = 0; e < C::ET; ++e) {
-      bf16x4 wk, wv;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { wk[r] = (bf16)(dk[e][r] * scale); wv[r] = (bf16)dv[e][r]; }
-      *reinterpret_cast<bf16x4*>(kp + 16 * e + 4 * lg) = wk;
-      *reinterpret_cast<bf16x4*>(vp + 16 * e + 4 * lg) = wv;
-    }
+    store_acc_bf16(dqkv + (row0 + key) * ldd + D + h * DH, dk, scale, lg);
+    store_acc_bf16(dqkv + (row0 + key) * ldd + 2 * D + h * DH, dv, 1.f, lg);
   }
 }
 
@@ -369,42 +257,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv(int L, int H, const bf16* __
 //    S, dP) and for the ds_read_b64_tr_b16 transposed reads (A operands over rows: dQ, dK, dV) —
 //    the templates' transposed copies, written element by element with ds_write_b16, are gone;
 //  * the ring loop is unrolled by its depth so every LDS address is an instruction immediate.
-namespace b32 {
-constexpr int NS = 4;
-constexpr int TILE = 64 * 64;                           // 64 rows x 32 bf16
-__device__ __forceinline__ int img(int row, int chunk) {
-  return row * 64 + (((chunk >> 1) ^ ((row >> 2) & 1)) << 5) + ((chunk & 1) << 4);
-}
-// the source chunk that lands at 16-B position p of an image row
-__device__ __forceinline__ int img_src(int row, int p) { return (((p >> 1) ^ ((row >> 2) & 1)) << 1) | (p & 1); }
-__device__ __forceinline__ bf16x4 trr(const char* p) {
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-  return __builtin_bit_cast(bf16x4, v);
-}
-// A fragment over 64 image rows (MFMA k = 8 lg + j: rows 32 c + 4 lg + {0..3}, 32 c + 16 + 4 lg + {0..3})
-// at columns 16 e + li: the transposed tile, read transposed
-__device__ __forceinline__ bf16x8 tfrag(const char* im, int e, int c, int li, int lg) {
-  const int q = li >> 2, p = li & 3, r0 = 32 * c + 4 * lg + q, cb = 2 * e + (p >> 1), off = 8 * (p & 1);
-  const bf16x4 lo = trr(im + img(r0, cb) + off), hi = trr(im + img(r0 + 16, cb) + off);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-__device__ __forceinline__ bf16x8 rowfrag(const char* im, int row, int lg) {
-  return *reinterpret_cast<const bf16x8*>(im + img(row, lg));
-}
-__device__ __forceinline__ i32x4 rsrc(const void* base, long bytes) { return dma_rsrc(base, bytes); }
-// LDS-DMA by inline asm (common.h dma_x4): no compiler-inserted ring drains
-__device__ __forceinline__ void dma(const i32x4& r, const char* lds, int voff, int soff) {
-  dma_x4(r, lds_addr(lds), voff, soff);
-}
-}  // namespace b32
 
 __global__ __launch_bounds__(256) void attn_bwd_dkv32(int L, int H, const bf16* __restrict__ qkv, long ld,
                                                       const bf16* __restrict__ dO, long lddo,
                                                       const float* __restrict__ lse, const float* __restrict__ Dq,
                                                       bf16* __restrict__ dqkv, long ldd, float c_log2e, float scale,
                                                       int nkb, AttnDrop drop, long total_rows) {
-  using namespace b32;
+  using namespace t32;
   constexpr int SLOT = 2 * TILE + 512;                  // Q image, dO image, 4 x [lse 16, D 16] f32
   __shared__ __attribute__((aligned(16))) char smem[NS * SLOT];
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
@@ -419,13 +278,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv32(int L, int H, const bf16* 
   const bf16x8 kf = key < L ? *reinterpret_cast<const bf16x8*>(qkv + (row0 + key) * ld + D + h * 32 + 8 * lg) : bf16x8{};
   bf16x8 vf = key < L ? *reinterpret_cast<const bf16x8*>(qkv + (row0 + key) * ld + 2 * D + h * 32 + 8 * lg) : bf16x8{};
   bf16x8 kf_ = kf;
-  asm volatile("" : "+v"(kf_), "+v"(vf));        // retire the loads before the DMA ring (dma_x4)
+  retire_loads(kf_, vf);
 
   // this wave's pieces of a tile: Q / dO rows 16 wave + lane / 4 (image position lane % 4), and
   // lanes 0..3: lse / D of queries 16 wave + 4 lane .. + 3 (rows past L: the buffer's zeros)
-  const i32x4 rq = rsrc(qkv + row0 * ld, (total_rows - row0) * ld * 2);
-  const i32x4 ro = rsrc(dO + row0 * lddo, (total_rows - row0) * lddo * 2);
-  const i32x4 rl = rsrc(lse + srow, (long)L * 4), rd = rsrc(Dq + srow, (long)L * 4);
+  const i32x4 rq = dma_rsrc(qkv + row0 * ld, (total_rows - row0) * ld * 2);
+  const i32x4 ro = dma_rsrc(dO + row0 * lddo, (total_rows - row0) * lddo * 2);
+  const i32x4 rl = dma_rsrc(lse + srow, (long)L * 4), rd = dma_rsrc(Dq + srow, (long)L * 4);
   const int prow = 16 * wave + (lane >> 2), pc = img_src(prow, lane & 3);
   const int vq = (int)(prow * ld * 2) + (h * 32 + 8 * pc) * 2;
   const int vo = (int)(prow * lddo * 2) + (h * 32 + 8 * pc) * 2;
@@ -433,18 +292,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv32(int L, int H, const bf16* 
   const int tq = (int)(64 * ld * 2), to = (int)(64 * lddo * 2);
   auto issue = [&](int t, int slot) {
     char* sl = smem + slot * SLOT;
-    dma(rq, sl + wave * 1024, vq, t * tq);
-    dma(ro, sl + TILE + wave * 1024, vo, t * to);
+    dma_x4(rq, lds_addr(sl + wave * 1024), vq, t * tq);
+    dma_x4(ro, lds_addr(sl + TILE + wave * 1024), vo, t * to);
     if (lane < 4) {
-      dma(rl, sl + 2 * TILE + wave * 128, vl, t * 256);
-      dma(rd, sl + 2 * TILE + wave * 128 + 64, vl, t * 256);
+      dma_x4(rl, lds_addr(sl + 2 * TILE + wave * 128), vl, t * 256);
+      dma_x4(rd, lds_addr(sl + 2 * TILE + wave * 128 + 64), vl, t * 256);
     }
   };
-  auto wait = [&](int y) {                              // all but the y youngest tiles (4 per tile)
-    if (y >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (y == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
+  constexpr int PPT = 4;                                // DMA instructions per wave per tile
 
   f32x4 dk[2], dv[2];
 #pragma unroll
@@ -512,7 +367,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv32(int L, int H, const bf16* 
     if (j < ntile) issue(j, j);
   auto step = [&](auto s_tag, int t) __attribute__((always_inline)) {
     constexpr int S = decltype(s_tag)::value;
-    wait(NS - 2);                       // unrolled loop (t + NS <= ntile): NS - 2 younger tiles in flight
+    ring_wait<PPT>(NS - 2);                       // unrolled loop (t + NS <= ntile): NS - 2 younger tiles in flight
     __builtin_amdgcn_s_barrier();
     issue(t + NS - 1, (S + NS - 1) % NS);
     if ((t + 1) * 64 <= L) body(smem + S * SLOT, t, std::false_type{});
@@ -526,7 +381,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv32(int L, int H, const bf16* 
     step(std::integral_constant<int, 3>{}, t + 3);
   }
   for (; t < ntile; ++t) {
-    wait(min(NS - 2, ntile - 1 - t));
+    ring_wait<PPT>(min(NS - 2, ntile - 1 - t));
     __builtin_amdgcn_s_barrier();
     if (t + NS - 1 < ntile) issue(t + NS - 1, (t + NS - 1) % NS);
     if ((t + 1) * 64 <= L) body(smem + (t % NS) * SLOT, t, std::false_type{});
@@ -552,7 +407,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq32(int L, int H, const bf16* _
                                                      const float* __restrict__ lse, float* __restrict__ Dout,
                                                      bf16* __restrict__ dqkv, long ldd, float c_log2e, float scale,
                                                      int nqb, AttnDrop drop, long total_rows) {
-  using namespace b32;
+  using namespace t32;
   constexpr int SLOT = 2 * TILE;                        // K image, V image
   __shared__ __attribute__((aligned(16))) char smem[NS * SLOT];
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
@@ -576,23 +431,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dq32(int L, int H, const bf16* _
   const uint32_t dbase = drop_base(drop.seed, (uint32_t)sh);
   if (qv && lg == 0) Dout[srow + q] = dq_;
   bf16x8 qf_ = qf, df_ = df;
-  asm volatile("" : "+v"(qf_), "+v"(df_), "+v"(lse_q));   // retire the loads before the DMA ring (dma_x4)
+  retire_loads(qf_, df_, lse_q);
 
-  const i32x4 rk = rsrc(qkv + row0 * ld, (total_rows - row0) * ld * 2);
+  const i32x4 rk = dma_rsrc(qkv + row0 * ld, (total_rows - row0) * ld * 2);
   const int prow = 16 * wave + (lane >> 2), pc = img_src(prow, lane & 3);
   const int vk = (int)(prow * ld * 2) + (D + h * 32 + 8 * pc) * 2;
   const int vv = (int)(prow * ld * 2) + (2 * D + h * 32 + 8 * pc) * 2;
   const int tb = (int)(64 * ld * 2);
   auto issue = [&](int t, int slot) {
     char* sl = smem + slot * SLOT;
-    dma(rk, sl + wave * 1024, vk, t * tb);
-    dma(rk, sl + TILE + wave * 1024, vv, t * tb);
+    dma_x4(rk, lds_addr(sl + wave * 1024), vk, t * tb);
+    dma_x4(rk, lds_addr(sl + TILE + wave * 1024), vv, t * tb);
   };
-  auto wait = [&](int y) {                              // 2 per tile
-    if (y >= 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (y == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
+  constexpr int PPT = 2;                                // DMA instructions per wave per tile
   f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   const int ntile = (L + 63) / 64;
   auto body = [&](const char* st, int t, auto mask_tag) __attribute__((always_inline)) {
@@ -635,7 +486,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq32(int L, int H, const bf16* _
     if (j < ntile) issue(j, j);
   auto step = [&](auto s_tag, int t) __attribute__((always_inline)) {
     constexpr int S = decltype(s_tag)::value;
-    wait(NS - 2);                       // unrolled loop (t + NS <= ntile): NS - 2 younger tiles in flight
+    ring_wait<PPT>(NS - 2);                       // unrolled loop (t + NS <= ntile): NS - 2 younger tiles in flight
     __builtin_amdgcn_s_barrier();
     issue(t + NS - 1, (S + NS - 1) % NS);
     if ((t + 1) * 64 <= L) body(smem + S * SLOT, t, std::false_type{});
@@ -649,7 +500,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq32(int L, int H, const bf16* _
     step(std::integral_constant<int, 3>{}, t + 3);
   }
   for (; t < ntile; ++t) {
-    wait(min(NS - 2, ntile - 1 - t));
+    ring_wait<PPT>(min(NS - 2, ntile - 1 - t));
     __builtin_amdgcn_s_barrier();
     if (t + NS - 1 < ntile) issue(t + NS - 1, (t + NS - 1) % NS);
     if ((t + 1) * 64 <= L) body(smem + (t % NS) * SLOT, t, std::false_type{});

@@ -122,7 +122,7 @@ __device__ __forceinline__ i32x4 dma_rsrc(const void* base, long bytes) {
 // the ring collapses to synchronous loads).  The caller owns the ordering: a counted
 // s_waitcnt vmcnt (this wave's pieces) and a barrier (the other waves') before reading — and
 // must retire any compiler-visible global load whose first use is inside the ring loop before
-// the loop (asm volatile("" : "+v"(x))), or its wait lands in the loop as vmcnt(0).
+// the loop (retire_loads(x...)), or its wait lands in the loop as vmcnt(0).
 // ``lds`` is the wave-uniform LDS byte address (lds_addr()).
 __device__ __forceinline__ void dma_x4(const i32x4& rsrc, uint32_t lds, int voffset, int soffset) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
@@ -134,6 +134,21 @@ __device__ __forceinline__ void dma_x4(const i32x4& rsrc, uint32_t lds, int voff
 // (the shared aperture is the high dword), without the null check of an address-space cast
 __device__ __forceinline__ uint32_t lds_addr(const void* p) {
   return __builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)p);
+}
+// retire compiler-visible loads before a DMA ring loop (see dma_x4); one statement, so one wait
+template <typename A, typename B>
+__device__ __forceinline__ void retire_loads(A& a, B& b) { asm volatile("" : "+v"(a), "+v"(b)); }
+template <typename A, typename B, typename C>
+__device__ __forceinline__ void retire_loads(A& a, B& b, C& c) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c)); }
+
+// A 4-slot LDS-DMA ring (tile t in slot t % 4, 3 tiles in flight, one barrier per tile, a wave
+// issues PPT dma_x4 per tile): ring_wait retires this wave's pieces of all but the y youngest
+// tiles (y <= 2).
+template <int PPT>
+__device__ __forceinline__ void ring_wait(int y) {
+  if (y >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPT) : "memory");
+  else if (y == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPT) : "memory");
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 __device__ __forceinline__ float to_f32(float x) { return x; }

@@ -120,11 +120,6 @@ __global__ __launch_bounds__(256) void dw_dma_kernel(int M, int N, int K, const 
       dma_x4(rx, s + DW_R * 256 + j * 1024, vox[i], st * stx);
     }
   };
-  auto wait = [&](int y) {                           // 4 DMA per stage per wave
-    if (y >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (y == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
 
   const int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
   const int rowb = 8 * (g >> 1) + q;
@@ -169,14 +164,14 @@ __global__ __launch_bounds__(256) void dw_dma_kernel(int M, int N, int K, const 
   for (; st + DWD_NS <= nst; st += DWD_NS) {
 #pragma unroll
     for (int u = 0; u < DWD_NS; ++u) {
-      wait(min(DWD_NS - 2, nst - 1 - (st + u)));
+      ring_wait<4>(min(DWD_NS - 2, nst - 1 - (st + u)));   // 4 DMA per stage per wave
       __builtin_amdgcn_s_barrier();
       if (st + u + DWD_NS - 1 < nst) issue(st + u + DWD_NS - 1, (u + DWD_NS - 1) % DWD_NS);
       compute(slot_ptr(u));
     }
   }
   for (; st < nst; ++st) {
-    wait(min(DWD_NS - 2, nst - 1 - st));
+    ring_wait<4>(min(DWD_NS - 2, nst - 1 - st));
     __builtin_amdgcn_s_barrier();
     if (st + DWD_NS - 1 < nst) issue(st + DWD_NS - 1, (st + DWD_NS - 1) % DWD_NS);
     switch (st % DWD_NS) {                           // compile-time slot objects
