@@ -369,6 +369,15 @@ int snvrag_tail_forward(int64_t M, int D, const void* att, void* x, const void* 
                         const float* ln1_g, const float* ln1_b, const float* ffn_vec, float eps, void* stream);
 int snvrag_tail_ffn_forward(int64_t M, int D, const void* x1, void* out, const void* wstream,
                             const float* ffn_vec, float eps, void* stream);
+/* snvrag_tail_forward that also computes the NEXT layer's QKV projection of the rows it has just
+ * normalised, in the same launch: qkv_out[M, 3 D] = x W_qkv^T + b_qkv with x the tail's output (still
+ * written in place: the next tail's residual), qkv_pw = snvrag_proj_pack(D, 3, W_qkv), b_qkv f32 [3 D].
+ * D = 384 on the wide-row tail only (options tail_wide 1 / 2, tail_variant 0) and M * 3 D * 2 bytes
+ * < 2^31; anything else is an argument error.  x and qkv_out are bit-identical to snvrag_tail_forward
+ * followed by snvrag_proj_forward (option proj_wide 1). */
+int snvrag_tail_qkv_forward(int64_t M, int D, const void* att, void* x, const void* wstream, const float* b_o,
+                            const float* ln1_g, const float* ln1_b, const float* ffn_vec, float eps,
+                            const void* qkv_pw, const float* b_qkv, void* qkv_out, void* stream);
 /* Diagnostics: buffer of [workgroups][4 waves][10] uint64 phase stamps filled by the block tail at
  * D = 384 when SNVRAG_TAIL_VARIANT=4 (a separate stamped instantiation; NULL turns it off). */
 int snvrag_tail_stamps(void* buf);

@@ -82,6 +82,8 @@ struct Options {
                            // 0.62 vs 0.68 ms, bit-identical); 0: tail.hip PROJ mode
   int64_t tail_wide;       // block tail at D = 384 (PRE): 1 (default) the wide-row form (tailw.hip), 0 tail_kernel,
                            // 2 the wide-row form with phase stamps into the snvrag_tail_stamps buffer
+  int64_t tail_qkv;        // 1 (default): the encoder's wide-row tails also compute the NEXT layer's QKV projection
+                           // (snvrag_tail_qkv_forward: no stand-alone QKV GEMM after layer 0); 0: one QKV launch per layer
   int64_t deterministic;   // 1: the Python wrappers route dW, the neighbour-mean backward and the focal loss to the
                            // fixed-order *_det entry points (no float atomics); 0 (default): the atomic forms.
                            // Read by src/kernels.py, not by a launch path: each entry point is one form
@@ -90,9 +92,11 @@ Options& options();
 // the diagnostic stamp buffer set by snvrag_tail_stamps (null unless a tool set one)
 unsigned long long* diag_stamps();
 
-// the wide-row block tail (tailw.hip), D = 384, PRE mode (out = LN2(FFN(LN1(x + att W_o^T))) in place)
+// the wide-row block tail (tailw.hip), D = 384, PRE mode (out = LN2(FFN(LN1(x + att W_o^T))) in place);
+// pw != null: qkv_out[M, 3 D] = out W^T + pbias as well, W the snvrag_proj_pack stream pw (var 0 / 1 only)
 int tailw_launch(int M, const void* att, const void* resid, void* out, const void* ws, const float* vec,
-                 const float* b_o, const float* g1, const float* be1, float eps, int desync, int var, hipStream_t s);
+                 const float* b_o, const float* g1, const float* be1, float eps, int desync, int var,
+                 const void* pw, const float* pbias, void* qkv_out, hipStream_t s);
 
 // the wide-row projection (tailw.hip), D = 384: out[M, NC D] = x W^T + b on a snvrag_proj_pack stream
 int projw_launch(int M, int NC, const void* x, const void* ws, const float* bias, void* out, int desync, hipStream_t s);

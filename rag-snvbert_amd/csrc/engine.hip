@@ -1,8 +1,10 @@
 // Encoder stack orchestration: every launch of the n_layers transformer blocks issued
 // from C++ (one C-ABI call per forward, capturable in a hipGraph).  bf16 at D in {128,
-// 256, 384}: 3 launches per layer (QKV stream GEMM, attention, block tail); otherwise (f32
-// parity path, other D) the row-panel GEMM form below with LN fused into the epilogues
-// (SNVRAG_UNFUSED_LN=1: the 8-launch unfused form, test-only).
+// 256, 384}: 3 launches per layer (QKV stream GEMM, attention, block tail) — at D = 384 on the
+// wide-row tail (option tail_qkv, default 1) the tail of layer i also computes layer i + 1's QKV
+// (snvrag_tail_qkv_forward), so only layer 0 launches a QKV GEMM: 1 + 2 n_layers launches;
+// otherwise (f32 parity path, other D) the row-panel GEMM form below with LN fused into the
+// epilogues (SNVRAG_UNFUSED_LN=1: the 8-launch unfused form, test-only).
 //
 // Per block (model/transformer.py:27-30, sublayer.py:15-16, feed_forward.py:18-21,
 // multi_head_attention.py:44-51), eval:
@@ -11,8 +13,9 @@
 //   x1  = LN1(x + a Wo^T + bo)              (residual fused in the GEMM epilogue)
 //   h   = LN_f(lrelu(x1 W1^T + b1))         (LN in place)
 //   x   = LN2(x1 + lrelu(h W2^T + b2))      (residual fused after the activation)
-// Sequences are processed in chunks so a chunk's activations (9 D per token)
-// stay resident in the 256 MiB Infinity Cache across the 12 layers.
+// Sequences are processed in chunks that cap the workspace (9 D per token) at ~16 GB
+// (chunk_seqs below): a chunk is far larger than the 256 MiB Infinity Cache, every launch
+// streams its activations from HBM.
 #include "common.h"
 
 #include <cmath>
@@ -74,6 +77,7 @@ extern "C" int snvrag_encoder_forward(int dtype, int64_t nseq, int64_t L, int D,
     const int64_t ns = std::min<int64_t>(cs, nseq - s0);
     const int64_t M = ns * L;
     char* xc = (char*)x + (size_t)s0 * L * D * esz;
+    bool have_qkv = false;                               // layer i's qkv already written by layer i - 1's tail
     for (int i = 0; i < n_layers; ++i) {
       const snvrag_layer_t& ly = layers[i];
       snvrag_epilogue_t e{};
@@ -83,7 +87,9 @@ extern "C" int snvrag_encoder_forward(int dtype, int64_t nseq, int64_t L, int D,
       // at 2 GiB, beyond that the 32x32 projection stream (csrc/tail.hip PROJ mode)
       // (the wide-row projection, csrc/tailw.hip, measured 0.62-0.70 vs 0.54 ms for the 8-wave stream
       // GEMM at M = 527 360: the stream GEMM stays; tools/proj_micro.py)
-      if (dtype == SNVRAG_BF16 && ly.qkv_sg && M * 3 * D * 2 < (1L << 31))
+      if (have_qkv)
+        rc = 0;
+      else if (dtype == SNVRAG_BF16 && ly.qkv_sg && M * 3 * D * 2 < (1L << 31))
         rc = snvrag_sgemm_forward(M, (int)D, (int)(3 * D), 0, SNVRAG_ACT_NONE, 0.f, xc, ly.qkv_sg, ly.b_qkv, nullptr,
                                   nullptr, 0, 0.f, qkv, nullptr, nullptr, stream);
       else if (dtype == SNVRAG_BF16 && ly.qkv_pw)
@@ -96,8 +102,17 @@ extern "C" int snvrag_encoder_forward(int dtype, int64_t nseq, int64_t L, int D,
       rc = snvrag_attention(dtype, ns, L, heads, dh, qkv, 3 * D, att, D, sc, stream);
       if (rc) return rc;
       if (fused && dtype == SNVRAG_BF16 && ly.tail_w && ly.ffn_v) {
-        // the whole block tail on 32x32 MFMAs (csrc/tail.hip): one launch
-        rc = snvrag_tail_forward(M, D, att, xc, ly.tail_w, ly.b_o, ly.ln1_g, ly.ln1_b, ly.ffn_v, 1e-5f, stream);
+        // the whole block tail on 32x32 MFMAs (csrc/tail.hip): one launch; on the wide-row tail
+        // (csrc/tailw.hip) it also projects its rows to the next layer's qkv while they are on chip
+        // (the folded q scale is in the packed weights and the bias: attention sees no difference)
+        have_qkv = i + 1 < n_layers && D == 384 && options().tail_qkv && options().tail_variant == 0 &&
+                   (options().tail_wide == 1 || options().tail_wide == 2) && layers[i + 1].qkv_pw &&
+                   layers[i + 1].b_qkv && M * 3 * D * 2 < (1L << 31);
+        if (have_qkv)
+          rc = snvrag_tail_qkv_forward(M, D, att, xc, ly.tail_w, ly.b_o, ly.ln1_g, ly.ln1_b, ly.ffn_v, 1e-5f,
+                                       layers[i + 1].qkv_pw, layers[i + 1].b_qkv, qkv, stream);
+        else
+          rc = snvrag_tail_forward(M, D, att, xc, ly.tail_w, ly.b_o, ly.ln1_g, ly.ln1_b, ly.ffn_v, 1e-5f, stream);
         if (rc) return rc;
         continue;
       }

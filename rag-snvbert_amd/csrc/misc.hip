@@ -106,6 +106,7 @@ const OptDesc kOpts[] = {
     {"tail_wide", &Options::tail_wide, 1},         {"proj_wide", &Options::proj_wide, 1},
     {"g2_variant", &Options::g2_variant, 0},     {"g2_groups", &Options::g2_groups, 0},
     {"tail_split", &Options::tail_split, 64},      {"deterministic", &Options::deterministic, 0},
+    {"tail_qkv", &Options::tail_qkv, 1},
 };
 Options make_options() {
   Options o{};

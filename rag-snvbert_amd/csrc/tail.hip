@@ -1103,6 +1103,9 @@ static int launch_tailp(TailArgs a, hipStream_t s) {
   return 0;
 }
 
+// the wide-row tail's first-round stagger (launch_tail below and snvrag_tail_qkv_forward)
+static int tailw_desync(int M) { return stagger_step(cdiv(M, TL_ROWS), 8 * 256, options().tail_desync, 10000); }
+
 template <int D, bool PRE>
 static int launch_tail(TailArgs a, hipStream_t s) {
   const int var = (int)options().tail_variant;
@@ -1114,9 +1117,9 @@ static int launch_tail(TailArgs a, hipStream_t s) {
       // 1.454 / 1.399 at tail_kernel's 25 k and 1.444 without; r6: 4 k was 1 % faster alone
       // (tools/tailw_desync_sweep.py) but 0.7 % slower inside the bench step, 1.363 vs 1.353 ms,
       // profiles/r6_tail_desync_bench_ab.txt — 10 k kept)
-      const int desync = stagger_step(cdiv(a.M, TL_ROWS), 8 * 256, options().tail_desync, 10000);
-      return tailw_launch(a.M, a.act, a.resid, a.out, a.ws, a.vec, a.b_o, a.g1, a.be1, a.eps, desync,
-                          (int)options().tail_wide >= 2 ? (int)options().tail_wide - 1 : 0, s);
+      return tailw_launch(a.M, a.act, a.resid, a.out, a.ws, a.vec, a.b_o, a.g1, a.be1, a.eps, tailw_desync(a.M),
+                          (int)options().tail_wide >= 2 ? (int)options().tail_wide - 1 : 0, nullptr, nullptr,
+                          nullptr, s);
     }
   // the persistent kernel (option tail_persist; measured no faster, see tailp_kernel): 32-bit
   // byte offsets of the in-place rows
@@ -1211,6 +1214,32 @@ extern "C" int snvrag_tail_forward(int64_t M, int D, const void* att, void* x, c
   const TailArgs a{(int)M, (const bf16*)att, (const bf16*)x, (bf16*)x, (const char*)wstream, ffn_vec, b_o, ln1_g,
                    ln1_b, eps, nullptr, 0};
   return tail_common(M, D, true, a, stream);
+}
+
+// the block tail and the next layer's QKV projection in one launch (tailw.hip, the projection phase)
+extern "C" int snvrag_tail_qkv_forward(int64_t M, int D, const void* att, void* x, const void* wstream,
+                                       const float* b_o, const float* ln1_g, const float* ln1_b,
+                                       const float* ffn_vec, float eps, const void* qkv_pw, const float* b_qkv,
+                                       void* qkv_out, void* stream) {
+  SNV_CHECK_ARG(D == 384, "the fused tail + QKV needs D = 384");
+  SNV_CHECK_ARG(options().tail_variant == 0 && (options().tail_wide == 1 || options().tail_wide == 2),
+                "the fused tail + QKV runs on the wide-row tail only (tail_wide 1 / 2, tail_variant 0)");
+  SNV_CHECK_ARG(att && x && wstream && b_o && ln1_g && ln1_b && ffn_vec && qkv_pw && b_qkv && qkv_out, "null pointer");
+  SNV_CHECK_ARG(att != x && qkv_out != x && qkv_out != att, "att, x and qkv_out must not alias");
+  SNV_CHECK_ARG(M >= 0 && M < (1L << 31), "bad M");
+  SNV_CHECK_ARG((long)M * 3 * D * 2 < (1L << 31), "qkv_out past 2 GiB: run snvrag_tail_forward and a projection");
+  SNV_CHECK_ARG(((uintptr_t)att % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)wstream % 16) == 0 &&
+                    ((uintptr_t)ffn_vec % 16) == 0 && ((uintptr_t)qkv_pw % 16) == 0 && ((uintptr_t)b_qkv % 16) == 0 &&
+                    ((uintptr_t)qkv_out % 16) == 0,
+                "pointers must be 16-byte aligned");
+  if (M == 0) return 0;
+  hipStream_t s = as_stream(stream);
+  evlog_begin(s);
+  const int rc = tailw_launch((int)M, att, x, x, wstream, ffn_vec, b_o, ln1_g, ln1_b, eps, tailw_desync((int)M),
+                              (int)options().tail_wide - 1, qkv_pw, b_qkv, qkv_out, s);
+  if (rc) return rc;
+  evlog_end(s, EV_BLOCK, (18.0 + 6.0) * M * (double)D * D);     // the tail's 18 M D^2 + the projection's 6 M D^2
+  return 0;
 }
 
 extern "C" int snvrag_tail_ffn_forward(int64_t M, int D, const void* x1, void* out, const void* wstream,

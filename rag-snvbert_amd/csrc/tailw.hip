@@ -130,7 +130,8 @@ static_assert(TW_B1_WAIT_END <= 63 && tw_younger(0) <= 63, "vmcnt range");
 // hipcc stashes W fragments in AGPRs and reads one back right before its MFMA (a VALU write of an
 // operand: 2 wait states); the loop body has no such write (tests/test_asm_hazards.py scans for it)
 // TW_NOPMASK: which MFMA segments outside the FFN loop carry the s_nop (bit 0 phase A, bit 1 FFN1(0),
-// bit 2 the last FFN1 / FFN2 of the loop's tail, bit 3 FFN2(11)); the 32-row (G = 1) body always.
+// bit 2 the last FFN1 / FFN2 of the loop's tail, bit 3 FFN2(11), bit 4 the projection phase); the
+// 32-row (G = 1) body always.
 // r6: only FFN1(0) gets a VALU write of an MFMA operand within 2 wait states without it (a scan of
 // each segment with its s_nop removed: tests/test_asm_hazards.py keeps checking the build)
 #ifndef TW_NOPMASK
@@ -196,14 +197,100 @@ struct TwArgs {
   int desync;
   unsigned long long* stamps;   // VAR 1: [workgroup][wave][8] s_memtime stamps
   int n_full;                   // workgroups of 128 rows (the rest: 32 rows)
+  // the projection phase (null: none): qkv_out[M, 3 D] = out W^T + pbias, the next layer's QKV
+  const char* pw;               // snvrag_proj_pack stream, NC = 3
+  const float* pbias;           // [3 D]
+  bf16* qkv_out;                // [M, 3 D], M 3 D 2 bytes < 2^31
 };
+
+// ---- the wide-row projection's chunk loop: out[rows of the tile][NC D] = X W^T + bias, the tail's
+// phase A per output chunk c of D features, shared by projw_kernel (G = 4) and the block tail's
+// projection phase (G = 4 and the 32-row body's G = 1): per chunk 24 k16 steps x 3 tiles x G token
+// groups into the phase-A accumulators, then + bias -> bf16 -> two 16-B stores per (tile, token
+// group) through the bounds-checked resource `ors` (rows >= M are dropped).  The caller has the X
+// images complete and visible (a barrier), the bias table (f32 [NC D]) at LDS byte address
+// `bias_lds`, and the first TW_AH fragments of the wave's stream in flight in wf[0 .. TW_AH) (pw_loadW).
+// W fragments (snvrag_proj_pack: chunk c, k16 step s, tile T at fragment c 288 + 12 s + T): fragment n
+// of wave w's stream = chunk n / 72, k16 step (n % 72) / 3, tile 3w + n % 3 (past the last chunk: the
+// last chunk again, never consumed), compiler-visible loads through the 12-register ring, TW_AH ahead
+__device__ __forceinline__ void pw_loadW(u32x4& r, const __amdgpu_buffer_rsrc_t wrb, int lane16, int wave, int NC, int c,
+                                         int n72) {
+  const int cc = c < NC ? c : NC - 1;
+  r = __builtin_amdgcn_raw_buffer_load_b128(wrb, lane16, (cc * TW_FPRE + (n72 / 3) * TW_NT + 3 * wave + n72 % 3) * FRAG_BYTES, 0);
+}
+template <int G, bool NOP>
+__device__ __forceinline__ void pw_chunks(const char* smem, uint32_t bias_lds, int wave, int lane16,
+                                          const __amdgpu_buffer_rsrc_t wrb, int NC, const __amdgpu_buffer_rsrc_t ors,
+                                          u32x4 (&wf)[TW_RING], f32x16 (&acc)[3][4]) {
+  constexpr int D = TW_D, KS = TW_KS, GI = G > 1 ? 1 : 0;
+  auto rdB = [&](int blk) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + TW_X + blk * FRAG_BYTES + lane16); };
+  u32x4 bq[2][4];
+#pragma unroll 1
+  for (int c = 0; c < NC; ++c) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) bq[0][g] = rdB(g);
+    unroll([&](auto sc) {
+      constexpr int s = decltype(sc)::value, n0 = 3 * s;
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+          if constexpr (s == 0) mfma32_asm0<true, NOP>(acc[t][g], wf[(n0 + t) % TW_RING], bq[s & 1][g]);
+          else mfma32_asm<true, NOP>(acc[t][g], wf[(n0 + t) % TW_RING], bq[s & 1][g]);
+        }
+        if constexpr (s + 1 < KS) bq[(s + 1) & 1][g] = rdB((s + 1) * 4 + g);
+        if (g == GI) {
+#pragma unroll
+          for (int t = 0; t < 3; ++t) {
+            const int m = n0 + TW_AH + t;              // within [0, 72 + 9): this chunk or the next
+            if (m < 72) pw_loadW(wf[(n0 + TW_AH + t) % TW_RING], wrb, lane16, wave, NC, c, m);
+            else pw_loadW(wf[(n0 + TW_AH + t) % TW_RING], wrb, lane16, wave, NC, c + 1, m - 72);
+          }
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }, std::make_integer_sequence<int, KS>{});
+    tw_drain_o(acc);
+    // + bias -> bf16 -> out[row][c D + 32 T + 16 hh .. + 15]
+    const int l = lane_id();
+    const uint32_t bb = bias_lds + 4 * (c * D + 16 * (l >> 5));
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      const int T = 3 * wave + t;
+      float bv[16];
+      ld16(bb + 4 * 32 * T, bv);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const int ro = ((32 * g + (l & 31)) * NC * D + c * D + 32 * T + 16 * (l >> 5)) * 2;
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2) {
+          float y[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) y[j] = acc[t][g][8 * h2 + j] + bv[8 * h2 + j];
+          __builtin_amdgcn_raw_buffer_store_b128(u32x4{pack2(y[0], y[1]), pack2(y[2], y[3]), pack2(y[4], y[5]),
+                                                       pack2(y[6], y[7])},
+                                                 ors, ro + 16 * h2, 0, 0);
+        }
+      }
+    }
+  }
+}
+// the bounds-checked output resource of a tile whose first row is row0: rows [row0, M) of out[M, NC D]
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t pw_out_rsrc(bf16* out, int M, long row0, int NC) {
+  const long o_bytes = ((long)M - row0) * NC * TW_D * 2;
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(out + row0 * NC * TW_D), (short)0,
+                                           (int)(o_bytes < 0x7fffffffL ? o_bytes : 0x7fffffffL), 0x00020000);
+}
 
 // G token groups of 32 rows (G = 4: a 128-row tile; G = 1: the 32-row tiles that spread the last
 // partial round of 128-row tiles over more CUs, tailw_kernel below).  GI: the group after whose
-// MFMAs a step issues its W loads
-template <int VAR, int G>
-__device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
+// MFMAs a step issues its W loads.  PROJ: the projection phase after LN2 (p.pw set): the tile's output
+// rows, in registers as bf16 when LN2 stores them, also go into the X images (LN1's layout for x1) and
+// are multiplied by the next layer's W_qkv (pw_chunks, NC = 3) — the rows never come back from HBM
+template <int VAR, int G, bool PROJ>
+__device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, const int wave) {
   constexpr int D = TW_D, NT = TW_NT, GI = G > 1 ? 1 : 0;
+  constexpr uint32_t TW_PB = TW_H + 16 * 1024;        // LDS: the projection's bias table (3 D f32, 5 KiB of H half 0)
   // VAR bit 3: the FFN epilogue in FFN2's MFMA gaps instead of FFN1's (A/B)
   constexpr bool EPI_FFN2 = (VAR & 8) != 0;
   // the residual rows loaded during phase A (after step TW_RES_STEP's W loads: the prologue's HBM
@@ -213,11 +300,13 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
   // s_nop ahead of the inline-asm MFMAs of a segment (TW_NOPMASK bit b, or the 32-row body)
   constexpr bool NOPA = G == 1 || (TW_NOPMASK & 1), NOP0 = G == 1 || (TW_NOPMASK & 2);
   constexpr bool NOPT = G == 1 || (TW_NOPMASK & 4), NOPF = G == 1 || (TW_NOPMASK & 8);
+  constexpr bool NOPP = G == 1 || (TW_NOPMASK & 16);
   using TNA = std::integral_constant<bool, NOP0>;
   using TNT = std::integral_constant<bool, NOPT>;
   using TNF = std::integral_constant<bool, NOPF>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // (wave: made once by the kernel; the thread index is re-made from it and a fresh lane id where
+  // used, so that the launch's v0 does not stay live through the bodies the kernel holds)
   unsigned long long st[8] = {};
   auto stamp = [&](int i) {
     if constexpr (VAR & 1) st[i] = __builtin_amdgcn_s_memtime();
@@ -285,7 +374,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
   };
   if constexpr (!LATE_RES) load_res();
   float* tab = reinterpret_cast<float*>(smem + TW_H);                        // [b_o | g1 | be1]
-  for (int i = threadIdx.x; i < D; i += 256) {
+  for (int i = 64 * wave + lane_id(); i < D; i += 256) {
     tab[i] = p.b_o[i];
     tab[D + i] = p.g1[i];
     tab[2 * D + i] = p.be1[i];
@@ -686,6 +775,13 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
       const int pc = wave + 4 * j;
       if (pc < 6) dma_x4(vrs, lds0 + TW_H + pc * FRAG_BYTES, lane16, pc * FRAG_BYTES);
     }
+    // the projection's bias table (3 D f32 = 4.5 pieces; the last piece's upper half reads past the
+    // resource: zeros) into H half 0 behind the tables and the row statistics, the same way
+    if constexpr (PROJ) {
+      const i32x4 prs = dma_rsrc(p.pbias, 3L * D * 4);
+      dma_x4(prs, lds0 + TW_PB + wave * FRAG_BYTES, lane16, wave * FRAG_BYTES);
+      if (wave == 0) dma_x4(prs, lds0 + TW_PB + 4 * FRAG_BYTES, lane16, 4 * FRAG_BYTES);
+    }
   }
   seg2(11, std::integral_constant<int, 1>{}, std::integral_constant<int, TW_QF>{}, std::false_type{},
        std::true_type{}, TNF{}, std::false_type{});
@@ -697,6 +793,8 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the overrun loads have landed
   stamp(4);
+  const __amdgpu_buffer_rsrc_t pwb =
+      __builtin_amdgcn_make_buffer_rsrc((void*)p.pw, (short)0, PROJ ? 3 * TW_FPRE * FRAG_BYTES : 0, 0x00020000);
 
   // ---- epilogue: out = LN2(x1 + lrelu(rstd_f (acc - mean_f c1) + b2'))
   float2* s2 = reinterpret_cast<float2*>(smem + TW_H + 8 * 1024);
@@ -799,6 +897,12 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
     }
   }
   tw_barrier();
+  // the projection stream's first fragments, issued here so that their latency sits under LN2's
+  // normalise-and-store pass (ahead of the LN_f pass they cost that pass 36 registers: spills)
+  if constexpr (PROJ) {
+#pragma unroll
+    for (int n = 0; n < TW_AH; ++n) pw_loadW(wf[n], pwb, lane16, wave, 3, 0, n);
+  }
   {
     const int l = lane_id();
     float mean[4], rstd[4];
@@ -836,7 +940,19 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
 #else
         for (int i = 0; i < 16; ++i) y[i] = fmaf(fmaf(acc[t][g][i], rstd[g], nmr), g2[i], be2[i]);
 #endif
-        if (r < p.M) {
+        if constexpr (PROJ) {
+          // the same bf16 values also into the X images, x1's layout (LN1 above): this lane's cells
+          // are exactly those it read as the LN2 residual (xa / xb) before the barrier above, so no
+          // wave still reads what another overwrites; rows >= M as zeros, as projw_kernel reads them
+#pragma unroll
+          for (int h2 = 0; h2 < 2; ++h2) {
+            u32x4 v{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
+                    pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
+            if (r < p.M) *reinterpret_cast<u32x4*>(p.out + r * D + 32 * T + 16 * (l >> 5) + 8 * h2) = v;
+            else v = u32x4{0u, 0u, 0u, 0u};
+            *reinterpret_cast<u32x4*>(smem + TW_X + ((2 * T + h2) * 4 + g) * FRAG_BYTES + 16 * l) = v;
+          }
+        } else if (r < p.M) {
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2)
             *reinterpret_cast<u32x4*>(p.out + r * D + 32 * T + 16 * (l >> 5) + 8 * h2) =
@@ -846,11 +962,18 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
       }
     }
   }
+  stamp(5);
+  if constexpr (PROJ) {
+    // ---- projection: qkv_out rows of this tile = (the X images) W_qkv^T + b_qkv, three chunks of D
+    // features (the bias table: DMA'd into H during FFN2(11), visible since the epilogue's barriers)
+    tw_barrier();                                     // the tile's rows complete in X
+    pw_chunks<G, NOPP>(smem, lds0 + TW_PB, wave, lane16, pwb, 3, pw_out_rsrc(p.qkv_out, p.M, row0, 3), wf, acc);
+    stamp(7);
+  }
   if constexpr (VAR & 1) {
-    stamp(5);
-    if ((threadIdx.x & 63) == 0 && p.stamps) {
+    if (lane_id() == 0 && p.stamps) {
 #pragma unroll
-      for (int i = 0; i < 7; ++i) p.stamps[((long)blockIdx.x * 4 + wave) * 8 + i] = st[i];
+      for (int i = 0; i < 8; ++i) p.stamps[((long)blockIdx.x * 4 + wave) * 8 + i] = st[i];
     }
   }
 }
@@ -860,13 +983,24 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0) {
 template <int VAR>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void tailw_kernel(TwArgs p) {
-  if ((int)blockIdx.x < p.n_full) tailw_body<VAR, 4>(p, (long)blockIdx.x * 128);
-  else tailw_body<VAR, 1>(p, (long)p.n_full * 128 + (long)(blockIdx.x - p.n_full) * 32);
+  // with a projection stream (the default and the stamped instantiation only): the bodies with the
+  // projection phase — a tile's rows never need a second kernel, the 32-row tiles included
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if constexpr (VAR <= 1) {
+    if (p.pw) {
+      if ((int)blockIdx.x < p.n_full) tailw_body<VAR, 4, true>(p, (long)blockIdx.x * 128, wave);
+      else tailw_body<VAR, 1, true>(p, (long)p.n_full * 128 + (long)(blockIdx.x - p.n_full) * 32, wave);
+      return;
+    }
+  }
+  if ((int)blockIdx.x < p.n_full) tailw_body<VAR, 4, false>(p, (long)blockIdx.x * 128, wave);
+  else tailw_body<VAR, 1, false>(p, (long)p.n_full * 128 + (long)(blockIdx.x - p.n_full) * 32, wave);
 }
 
 int tailw_launch(int M, const void* att, const void* resid, void* out, const void* ws, const float* vec,
                  const float* b_o, const float* g1, const float* be1, float eps, int desync, int var,
-                 hipStream_t s) {
+                 const void* pw, const float* pbias, void* qkv_out, hipStream_t s) {
+  if (pw && (var & ~1)) return fail(__func__, "the projection phase runs in the default and the stamped tail only");
   // the last partial round of 128-row tiles (rem of 256 CUs) as 4 rem workgroups of 32 rows, when
   // they fit one round of 32-row tiles (option tail_split = the largest rem split; 0: off)
   const long T = cdiv(M, 128), rem = T % 256;
@@ -874,7 +1008,7 @@ int tailw_launch(int M, const void* att, const void* resid, void* out, const voi
   const long n_full = (T > 256 && rem > 0 && rem <= split) ? T - rem : T;
   const long nwg = n_full < T ? n_full + cdiv((long)M - n_full * 128, 32) : T;
   TwArgs a{M, (const bf16*)att, (const bf16*)resid, (bf16*)out, (const char*)ws, vec, b_o, g1, be1, eps, desync,
-           diag_stamps(), (int)n_full};
+           diag_stamps(), (int)n_full, (const char*)pw, pbias, (bf16*)qkv_out};
   // var (option tail_wide - 1): bit 0 phase stamps, bit 1 / bit 2 the W-latency / FFN1-LDS
   // diagnostics (wrong results: tools/tailw_diag.py timing only; r6: W-cached no faster, no-FFN1-LDS
   // 2 %), bit 3 the FFN epilogue in FFN2's gaps (A/B)
@@ -895,7 +1029,8 @@ int tailw_launch(int M, const void* att, const void* resid, void* out, const voi
 // workgroup owns 128 rows (x by LDS-DMA into X once), wave w owns tiles 3w .. 3w+2 of each chunk;
 // per chunk 24 k16 steps x 12 MFMAs into 192 AGPR accumulators, then + bias -> bf16 -> two 16-B
 // stores per (tile, token group).  W fragments (snvrag_proj_pack: chunk c, k16 step s, tile T at
-// fragment c 288 + 12 s + T) through the 12-register ring 9 ahead, compiler-visible loads.
+// fragment c 288 + 12 s + T) through the 12-register ring 9 ahead, compiler-visible loads: the chunk
+// loop is pw_chunks above, which the block tail's projection phase runs too.
 struct PwArgs {
   int M, NC;
   const bf16* x;            // [M, D]
@@ -923,78 +1058,17 @@ void projw_kernel(PwArgs p) {
     for (int s = 0; s < KS; ++s)
       dma_x4(xrs, lds0 + TW_X + (s * 4 + wave) * FRAG_BYTES, voff, 64 * (s >> 1) + 16 * (s & 1));
   }
-  const int nfr = p.NC * TW_FPRE;
-  const __amdgpu_buffer_rsrc_t wrb = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, nfr * FRAG_BYTES, 0x00020000);
+  const __amdgpu_buffer_rsrc_t wrb =
+      __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, p.NC * TW_FPRE * FRAG_BYTES, 0x00020000);
   u32x4 wf[TW_RING];
-  // fragment n of this wave's stream: chunk n / 72, k16 step (n % 72) / 3, tile 3w + n % 3 (past the
-  // last chunk: the last chunk again, never consumed)
-  auto loadW = [&](u32x4& r, int c, int n72) {
-    const int cc = c < p.NC ? c : p.NC - 1;
-    r = __builtin_amdgcn_raw_buffer_load_b128(wrb, lane16, (cc * TW_FPRE + (n72 / 3) * NT + 3 * wave + n72 % 3) * FRAG_BYTES, 0);
-  };
 #pragma unroll
-  for (int n = 0; n < TW_AH; ++n) loadW(wf[n], 0, n);
+  for (int n = 0; n < TW_AH; ++n) pw_loadW(wf[n], wrb, lane16, wave, p.NC, 0, n);
   float* bs = reinterpret_cast<float*>(smem + TW_H);
   for (int i = threadIdx.x; i < p.NC * D; i += 256) bs[i] = p.bias[i];
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the x image (LDS-DMA) landed
   tw_barrier();
-  auto rdB = [&](int blk) -> u32x4 { return *reinterpret_cast<const u32x4*>(smem + TW_X + blk * FRAG_BYTES + lane16); };
-  const long o_bytes = ((long)p.M - row0) * p.NC * D * 2;
-  const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(p.out + row0 * p.NC * D), (short)0, (int)(o_bytes < 0x7fffffffL ? o_bytes : 0x7fffffffL), 0x00020000);
   f32x16 acc[3][4];
-  u32x4 bq[2][4];
-#pragma unroll 1
-  for (int c = 0; c < p.NC; ++c) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) bq[0][g] = rdB(g);
-    unroll([&](auto sc) {
-      constexpr int s = decltype(sc)::value, n0 = 3 * s;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-          if constexpr (s == 0) mfma32_asm0<true, false>(acc[t][g], wf[(n0 + t) % TW_RING], bq[s & 1][g]);
-          else mfma32_asm<true, false>(acc[t][g], wf[(n0 + t) % TW_RING], bq[s & 1][g]);
-        }
-        if constexpr (s + 1 < KS) bq[(s + 1) & 1][g] = rdB((s + 1) * 4 + g);
-        if (g == 1) {
-#pragma unroll
-          for (int t = 0; t < 3; ++t) {
-            constexpr int dummy = 0;
-            const int m = n0 + TW_AH + t;              // within [0, 72 + 9): this chunk or the next
-            if (m < 72) loadW(wf[(n0 + TW_AH + t) % TW_RING], c, m);
-            else loadW(wf[(n0 + TW_AH + t) % TW_RING], c + 1, m - 72);
-            (void)dummy;
-          }
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }, std::make_integer_sequence<int, KS>{});
-    tw_drain_o(acc);
-    // + bias -> bf16 -> out[row][c D + 32 T + 16 hh .. + 15]
-    const int l = lane_id();
-    const uint32_t bb = lds0 + TW_H + 4 * (c * D + 16 * (l >> 5));
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const int T = 3 * wave + t;
-      float bv[16];
-      ld16(bb + 4 * 32 * T, bv);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int ro = ((32 * g + (l & 31)) * p.NC * D + c * D + 32 * T + 16 * (l >> 5)) * 2;
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-          float y[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) y[j] = acc[t][g][8 * h2 + j] + bv[8 * h2 + j];
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{pack2(y[0], y[1]), pack2(y[2], y[3]), pack2(y[4], y[5]),
-                                                       pack2(y[6], y[7])},
-                                                 ors, ro + 16 * h2, 0, 0);
-        }
-      }
-    }
-  }
+  pw_chunks<4, false>(smem, lds0 + TW_H, wave, lane16, wrb, p.NC, pw_out_rsrc(p.out, p.M, row0, p.NC), wf, acc);
 }
 
 int projw_launch(int M, int NC, const void* x, const void* ws, const float* bias, void* out, int desync, hipStream_t s) {

@@ -147,6 +147,26 @@ def tail_forward(att: torch.Tensor, x: torch.Tensor, wstream: torch.Tensor, b_o,
     return x
 
 
+def tail_qkv_forward(att: torch.Tensor, x: torch.Tensor, wstream: torch.Tensor, b_o, ln1_g, ln1_b,
+                     ffn_vec: torch.Tensor, qkv_pw: torch.Tensor, b_qkv: torch.Tensor,
+                     qkv_out: Optional[torch.Tensor] = None, eps: float = 1e-5):
+    """``tail_forward`` in place on x, and in the same launch qkv_out [M, 3 D] = x W_qkv^T + b_qkv of
+    the rows it has just written (qkv_pw = ``proj_pack(W_qkv)``): the next layer's QKV projection
+    (D = 384, wide-row tail only).  Returns (x, qkv_out)."""
+    N.require_gpu(att, x)
+    assert att.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and x.is_contiguous()
+    D = x.shape[-1]
+    M = x.numel() // D
+    if qkv_out is None:
+        qkv_out = torch.empty(M, 3 * D, device=x.device, dtype=torch.bfloat16)
+    assert qkv_out.dtype == torch.bfloat16 and qkv_out.is_contiguous() and qkv_out.numel() == M * 3 * D
+    f = [_c(t.float().contiguous()) for t in (b_o, ln1_g, ln1_b, b_qkv)]
+    check(N.lib().snvrag_tail_qkv_forward(M, D, ptr(_c(att)), ptr(x), ptr(wstream), ptr(f[0]), ptr(f[1]), ptr(f[2]),
+                                          ptr(_c(ffn_vec)), eps, ptr(qkv_pw), ptr(f[3]), ptr(qkv_out), stream_ptr()),
+          "tail_qkv_forward")
+    return x, qkv_out
+
+
 def tail_ffn_forward(x1: torch.Tensor, wstream: torch.Tensor, ffn_vec: torch.Tensor, eps: float = 1e-5,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = LN2(x1 + FFN(x1)) (32x32-MFMA kernel, FFN part of the tail stream)."""
