@@ -766,7 +766,7 @@ extern "C" int snvrag_attention_fallbacks(int reset) {
 extern "C" int snvrag_attention_train_fwd(int64_t nseq, int64_t L, int heads, int dh, const void* qkv,
                                           int64_t ld_qkv, void* out, int64_t ld_out, float* lse, float scale,
                                           float dropout_p, uint64_t seed, void* stream) {
-  SNV_CHECK_ARG(qkv && out && lse, "null pointer");
+  SNV_CHECK_PTRS(qkv, out, lse);
   SNV_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout probability must be in [0, 1)");
   const AttnDrop drop = make_attn_drop(dropout_p, seed);
   SNV_CHECK_ARG(nseq >= 0 && L > 0 && heads > 0, "bad shape");
@@ -801,7 +801,7 @@ extern "C" int snvrag_attention_train_fwd(int64_t nseq, int64_t L, int heads, in
 extern "C" int snvrag_attention(int dtype, int64_t nseq, int64_t L, int heads, int dh,
                                 const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out,
                                 float scale, void* stream) {
-  SNV_CHECK_ARG(qkv && out, "null pointer");
+  SNV_CHECK_PTRS(qkv, out);
   SNV_CHECK_ARG(nseq >= 0 && L > 0 && heads > 0, "bad shape");
   SNV_CHECK_ARG(ld_qkv >= 3L * heads * dh && ld_out >= (long)heads * dh, "leading dims too small");
   if (dtype == SNVRAG_BF16)

@@ -556,7 +556,7 @@ extern "C" int snvrag_attention_bwd(int64_t nseq, int64_t L, int heads, int dh, 
                                     const void* out, int64_t ld_out, const void* dout, int64_t ld_dout,
                                     const float* lse, float* d_ws, void* dqkv, int64_t ld_dqkv, float scale,
                                     float dropout_p, uint64_t seed, void* stream) {
-  SNV_CHECK_ARG(qkv && out && dout && lse && d_ws && dqkv, "null pointer");
+  SNV_CHECK_PTRS(qkv, out, dout, lse, d_ws, dqkv);
   SNV_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "dropout probability must be in [0, 1)");
   const AttnDrop drop = make_attn_drop(dropout_p, seed);
   SNV_CHECK_ARG(nseq >= 0 && L > 0 && heads > 0, "bad shape");

@@ -11,6 +11,7 @@
 #pragma clang diagnostic ignored "-Winline-asm"
 
 #include "../../include/snvrag.h"
+#include "host.h"   // the entry points' checks, dispatch and launch helpers
 
 namespace snvrag {
 
@@ -30,28 +31,6 @@ enum EvKind { EV_GEMM = 1, EV_ATTN = 2, EV_LN = 3, EV_KNN_SCAN = 4, EV_KNN_LUT =
 bool evlog_on();
 void evlog_begin(hipStream_t s);
 void evlog_end(hipStream_t s, int kind, double work);
-int fail(const char* where, const std::string& msg);
-
-#define SNV_CHECK_ARG(cond, msg)                                     \
-  do {                                                               \
-    if (!(cond)) return ::snvrag::fail(__func__, (msg));             \
-  } while (0)
-
-#define SNV_HIP(expr)                                                \
-  do {                                                               \
-    hipError_t e_ = (expr);                                          \
-    if (e_ != hipSuccess)                                            \
-      return ::snvrag::fail(__func__, hipGetErrorString(e_));        \
-  } while (0)
-
-// launch + error check (kernel launch errors surface via hipGetLastError)
-#define SNV_LAUNCH_CHECK()                                           \
-  do {                                                               \
-    hipError_t e_ = hipGetLastError();                               \
-    if (e_ != hipSuccess)                                            \
-      return ::snvrag::fail(__func__, hipGetErrorString(e_));        \
-  } while (0)
-
 // Library options: tuning switches of the micro-benchmarks (tools/) and test hooks.  Each is
 // initialised ONCE from the environment variable SNVRAG_<NAME> (upper case) at first use and can
 // be changed through snvrag_set_option; launch paths read this struct, never the environment.
@@ -100,9 +79,6 @@ int tailw_launch(int M, const void* att, const void* resid, void* out, const voi
 
 // the wide-row projection (tailw.hip), D = 384: out[M, NC D] = x W^T + b on a snvrag_proj_pack stream
 int projw_launch(int M, int NC, const void* x, const void* ws, const float* bias, void* out, int desync, hipStream_t s);
-
-static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ------------------------------------------------------------------ device --
 // A buffer resource (V#) in four SGPRs for the inline-asm LDS-DMA below: base, stride 0,

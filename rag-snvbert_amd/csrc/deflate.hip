@@ -106,9 +106,8 @@ extern "C" int snvrag_bgzf_deflate(const uint8_t* text, int64_t nbytes, int64_t 
                                    int32_t* member_len, void* stream) {
   SNV_CHECK_ARG(nbytes >= 0 && nbytes < (1LL << 31), "nbytes must be in [0, 2^31)");
   SNV_CHECK_ARG(block_size >= 1 && block_size <= DEFL_MAX_IN, "block_size must be in [1, 0xff00]");
-  SNV_CHECK_ARG(text && members && member_len, "null pointer");
-  SNV_CHECK_ARG(((uintptr_t)members % 16) == 0 && ((uintptr_t)member_len % 4) == 0,
-                "members must be 16-byte, member_len 4-byte aligned");
+  SNV_CHECK_PTRS(text, members, member_len);
+  SNV_CHECK_ARG(aligned(16, members) && aligned(4, member_len), "members must be 16-byte, member_len 4-byte aligned");
   if (nbytes == 0) return 0;
   const int64_t n_blocks = (nbytes + block_size - 1) / block_size;
   hipLaunchKernelGGL(bgzf_deflate_kernel, dim3((unsigned)n_blocks), dim3(DF_THREADS), 0, as_stream(stream), text,
@@ -121,8 +120,8 @@ extern "C" int snvrag_bgzf_pack(const uint8_t* members, const int32_t* member_le
                                 int64_t out_bytes, int64_t* total, void* stream) {
   SNV_CHECK_ARG(n_blocks >= 0 && n_blocks < (1LL << 31), "n_blocks must be in [0, 2^31)");
   SNV_CHECK_ARG(out_bytes >= 0, "out_bytes must not be negative");
-  SNV_CHECK_ARG(members && member_len && out && total, "null pointer");
-  SNV_CHECK_ARG(((uintptr_t)members % 16) == 0 && ((uintptr_t)member_len % 4) == 0 && ((uintptr_t)total % 8) == 0,
+  SNV_CHECK_PTRS(members, member_len, out, total);
+  SNV_CHECK_ARG(aligned(16, members) && aligned(4, member_len) && aligned(8, total),
                 "members must be 16-byte, member_len 4-byte, total 8-byte aligned");
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(bgzf_pack_total_kernel, dim3(1), dim3(DF_THREADS), 0, s, member_len, (long)n_blocks,

@@ -283,13 +283,12 @@ static int launch_dw(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ld
 static int launch_dw_det(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x, int64_t ldx,
                          const DwOut& out, int splits, void* ws, size_t ws_bytes, hipStream_t s) {
   if (M == 0) return 0;
-  SNV_CHECK_ARG(ws && ((uintptr_t)ws % 16) == 0, "workspace: null or not 16-byte aligned");
+  SNV_CHECK_ARG(ws && aligned(16, ws), "workspace: null or not 16-byte aligned");
   SNV_CHECK_ARG(ws_bytes >= snvrag_linear_dw_det_ws_bytes(M, N, K, splits),
                 "workspace smaller than snvrag_linear_dw_det_ws_bytes()");
   bool has_b = out.b[0] != nullptr;
   for (int i = 0; i < 4; ++i) {
-    SNV_CHECK_ARG(((uintptr_t)out.w[i] % 16) == 0 && ((uintptr_t)out.b[i] % 16) == 0,
-                  "dw / db must be 16-byte aligned");
+    SNV_CHECK_ALIGN(16, "dw / db must be 16-byte aligned", out.w[i], out.b[i]);
     SNV_CHECK_ARG(!out.w[i] || (out.b[i] != nullptr) == has_b, "db: all parts or none");
   }
   int chunk, S;
@@ -308,17 +307,17 @@ static int launch_dw_det(int64_t M, int64_t N, int64_t K, const void* dy, int64_
 }
 
 static int dw_check(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x, int64_t ldx) {
-  SNV_CHECK_ARG(dy && x, "null pointer");
+  SNV_CHECK_PTRS(dy, x);
   SNV_CHECK_ARG(M >= 0 && N % DW_T == 0 && K % DW_T == 0 && N > 0 && K > 0, "N and K must be multiples of 128");
   SNV_CHECK_ARG(ldy >= N && ldx >= K && ldy % 8 == 0 && ldx % 8 == 0, "leading dims: >= N / K, multiples of 8");
-  SNV_CHECK_ARG(((uintptr_t)dy % 16) == 0 && ((uintptr_t)x % 16) == 0, "operands must be 16-byte aligned");
+  SNV_CHECK_ALIGN(16, "operands must be 16-byte aligned", dy, x);
   return 0;
 }
 
 extern "C" int snvrag_linear_dw(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x,
                                 int64_t ldx, float* dw, float* db, int splits, void* stream) {
   if (int rc = dw_check(M, N, K, dy, ldy, x, ldx)) return rc;
-  SNV_CHECK_ARG(dw, "null pointer");
+  SNV_CHECK_PTRS(dw);
   // dw / db are accumulated: the caller zeroes them (or passes a running sum)
   DwOut out{{dw, nullptr, nullptr, nullptr}, {db, nullptr, nullptr, nullptr}, (int)N};
   return launch_dw(M, N, K, dy, ldy, x, ldx, out, splits, as_stream(stream));
@@ -327,7 +326,7 @@ extern "C" int snvrag_linear_dw(int64_t M, int64_t N, int64_t K, const void* dy,
 static int dw_parts_out(DwOut& out, int64_t N, int n_parts, float* const* dw_parts, float* const* db_parts) {
   SNV_CHECK_ARG(n_parts >= 1 && n_parts <= 4 && N % n_parts == 0 && (N / n_parts) % DW_T == 0,
                 "1-4 equal parts of N, each a multiple of 128");
-  SNV_CHECK_ARG(dw_parts, "null pointer");
+  SNV_CHECK_PTRS(dw_parts);
   out = DwOut{{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}, (int)(N / n_parts)};
   for (int i = 0; i < n_parts; ++i) {
     SNV_CHECK_ARG(dw_parts[i], "null dW part");
@@ -358,7 +357,7 @@ extern "C" int snvrag_linear_dw_det(int64_t M, int64_t N, int64_t K, const void*
                                     int64_t ldx, float* dw, float* db, int splits, void* ws, size_t ws_bytes,
                                     void* stream) {
   if (int rc = dw_check(M, N, K, dy, ldy, x, ldx)) return rc;
-  SNV_CHECK_ARG(dw, "null pointer");
+  SNV_CHECK_PTRS(dw);
   DwOut out{{dw, nullptr, nullptr, nullptr}, {db, nullptr, nullptr, nullptr}, (int)N};
   return launch_dw_det(M, N, K, dy, ldy, x, ldx, out, splits, ws, ws_bytes, as_stream(stream));
 }

@@ -376,7 +376,7 @@ extern "C" int snvrag_af_features(int dtype_out, int64_t M, const float* af, con
 extern "C" int snvrag_embed_tokens(int dtype_out, int64_t nseq, int64_t L, int64_t D, const int64_t* tok,
                                    const float* W, int64_t vocab, const float* pe, const void* afemb,
                                    int afemb_dtype, int64_t af_period, void* out, void* stream) {
-  SNV_CHECK_ARG(tok && W && pe && out, "null pointer");
+  SNV_CHECK_PTRS(tok, W, pe, out);
   SNV_CHECK_ARG(D % 8 == 0, "D must be a multiple of 8");
   if (nseq == 0) return 0;
   hipStream_t s = as_stream(stream);
@@ -396,7 +396,7 @@ extern "C" int snvrag_embed_tokens(int dtype_out, int64_t nseq, int64_t L, int64
 
 extern "C" int snvrag_posfeat(int64_t B, int64_t L, const float* pos, const snvrag_posfeat_w_t* w,
                               float* out, void* stream) {
-  SNV_CHECK_ARG(pos && w && out, "null pointer");
+  SNV_CHECK_PTRS(pos, w, out);
   if (B == 0) return 0;
   const size_t sh = (size_t)(L + 8) * 9 * sizeof(float);
   SNV_CHECK_ARG(sh <= 160 * 1024, "sequence too long for LDS");
@@ -407,7 +407,7 @@ extern "C" int snvrag_posfeat(int64_t B, int64_t L, const float* pos, const snvr
 
 extern "C" int snvrag_af_gate(int dtype_out, int64_t M, int64_t D, const float* af, const float* af_p,
                               const snvrag_afgate_w_t* w, void* out, void* stream) {
-  SNV_CHECK_ARG(af && af_p && w && out, "null pointer");
+  SNV_CHECK_PTRS(af, af_p, w, out);
   SNV_CHECK_ARG(D % 8 == 0, "D % 8");
   if (M == 0) return 0;
   hipStream_t s = as_stream(stream);
@@ -423,7 +423,7 @@ extern "C" int snvrag_af_gate(int dtype_out, int64_t M, int64_t D, const float* 
 
 extern "C" int snvrag_hap_head_out(int dtype_in, int64_t M, int64_t K, const void* H, int64_t ldh,
                                    const float* w, const float* b, float* logits, float* probs, void* stream) {
-  SNV_CHECK_ARG(H && w && b && probs, "null pointer");
+  SNV_CHECK_PTRS(H, w, b, probs);
   SNV_CHECK_ARG(K % 8 == 0 && ldh % 8 == 0, "K/ldh must be multiples of 8");
   if (M == 0) return 0;
   hipStream_t s = as_stream(stream);
@@ -437,7 +437,7 @@ extern "C" int snvrag_hap_head_out(int dtype_in, int64_t M, int64_t K, const voi
 
 extern "C" int snvrag_gt_head(int64_t M, const float* p1, const float* p2, const float* ref, const float* het,
                               const float* hom, int64_t period, const snvrag_gt_w_t* w, float* out, void* stream) {
-  SNV_CHECK_ARG(p1 && p2 && ref && het && hom && w && out, "null pointer");
+  SNV_CHECK_PTRS(p1, p2, ref, het, hom, w, out);
   if (M == 0) return 0;
   hipLaunchKernelGGL(gt_head_kernel, dim3(cdiv(M, 256)), dim3(256), 0, as_stream(stream), (long)M, p1, p2,
                      ref, het, hom, (long)period, *w, out);
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(256) void infer_scatter_kernel(int B, int L, const 
 
 extern "C" int snvrag_infer_post(int64_t M, const float* probs_h1, const float* probs_h2, float* p1, float* p2,
                                  float* gt, void* stream) {
-  SNV_CHECK_ARG(probs_h1 && probs_h2 && p1 && p2 && gt && ((uintptr_t)gt % 16) == 0, "null or misaligned pointer");
+  SNV_CHECK_ARG(probs_h1 && probs_h2 && p1 && p2 && gt && aligned(16, gt), "null or misaligned pointer");
   if (M == 0) return 0;
   hipLaunchKernelGGL(infer_post_kernel, dim3(cdiv(M, 256)), dim3(256), 0, as_stream(stream), (long)M, probs_h1,
                      probs_h2, p1, p2, gt);
@@ -539,10 +539,8 @@ extern "C" int snvrag_infer_scatter(int64_t B, int32_t L, const float* probs_h1,
                                     const int64_t* mask, const int32_t* rows_dev, const int32_t* rows_host,
                                     int32_t window_len, int64_t n_variants, int64_t S, float* hap1, float* hap2,
                                     float* gp, int64_t* mask_out, void* stream) {
-  SNV_CHECK_ARG(probs_h1 && probs_h2 && mask && rows_dev && rows_host && hap1 && hap2 && gp && mask_out,
-                "null pointer");
-  SNV_CHECK_ARG(((uintptr_t)gp % 16) == 0 && ((uintptr_t)probs_h1 % 8) == 0 && ((uintptr_t)probs_h2 % 8) == 0,
-                "gp must be 16-byte, probs 8-byte aligned");
+  SNV_CHECK_PTRS(probs_h1, probs_h2, mask, rows_dev, rows_host, hap1, hap2, gp, mask_out);
+  SNV_CHECK_ARG(aligned(16, gp) && aligned(8, probs_h1, probs_h2), "gp must be 16-byte, probs 8-byte aligned");
   SNV_CHECK_ARG(L >= 2 && window_len >= 1 && window_len <= L - 1, "window_len must be in [1, L - 1]");
   SNV_CHECK_ARG(B >= 0 && B * (int64_t)L < (1LL << 31), "B * L must be below 2^31");
   SNV_CHECK_ARG(n_variants >= 0 && S >= 1, "n_variants >= 0 and S >= 1");

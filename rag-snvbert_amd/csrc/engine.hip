@@ -51,7 +51,7 @@ extern "C" size_t snvrag_encoder_ws_bytes(int dtype, int64_t nseq, int64_t L, in
 extern "C" int snvrag_encoder_forward(int dtype, int64_t nseq, int64_t L, int D, int heads, int n_layers,
                                       const snvrag_layer_t* layers, void* x, void* ws, size_t ws_bytes,
                                       void* stream) {
-  SNV_CHECK_ARG(layers && x && ws, "null pointer");
+  SNV_CHECK_PTRS(layers, x, ws);
   SNV_CHECK_ARG(D % heads == 0, "D % heads");
   SNV_CHECK_ARG(ws_bytes >= snvrag_encoder_ws_bytes(dtype, nseq, L, D, heads), "encoder workspace too small");
   const int esz = dtype == SNVRAG_BF16 ? 2 : 4;

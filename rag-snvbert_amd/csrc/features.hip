@@ -127,7 +127,7 @@ extern "C" int snvrag_batch_features(const snvrag_feature_tables_t* tables, cons
                                      const int32_t* rows_host, int64_t B, int32_t L, int sos, int eos, int pad,
                                      int mask, int tok0, int tok1, int64_t* tokens, int64_t* mask_out,
                                      float* floats, int64_t* labels, void* stream) {
-  SNV_CHECK_ARG(tables && rows_dev && rows_host && tokens && mask_out && floats, "null pointer");
+  SNV_CHECK_PTRS(tables, rows_dev, rows_host, tokens, mask_out, floats);
   const snvrag_feature_tables_t& T = *tables;
   SNV_CHECK_ARG(T.gt_bits && T.win_off && T.site_row && T.freq_col && T.pos_norm && T.win_mask && T.freq &&
                 T.pop_of_sample, "null table pointer");
@@ -138,8 +138,8 @@ extern "C" int snvrag_batch_features(const snvrag_feature_tables_t* tables, cons
   SNV_CHECK_ARG(T.n_samples >= 1 && T.n_windows >= 1 && T.n_pop >= 1 && T.n_cols >= 1 && T.ld_bits >= 1,
                 "empty tables");
   SNV_CHECK_ARG(T.global_row >= 0 && T.global_row < T.n_pop, "global_row outside the frequency table");
-  SNV_CHECK_ARG(((uintptr_t)tokens % 16) == 0 && ((uintptr_t)mask_out % 16) == 0 && ((uintptr_t)labels % 16) == 0 &&
-                ((uintptr_t)floats % 8) == 0, "outputs must be 16-byte (i64) / 8-byte (f32) aligned");
+  SNV_CHECK_ARG(aligned(16, tokens, mask_out, labels) && aligned(8, floats),
+                "outputs must be 16-byte (i64) / 8-byte (f32) aligned");
   for (int64_t b = 0; b < B; ++b) {
     SNV_CHECK_ARG(rows_host[b] >= 0 && rows_host[b] < T.n_samples, "sample index out of range");
     SNV_CHECK_ARG(rows_host[B + b] >= 0 && rows_host[B + b] < T.n_windows, "window index out of range");

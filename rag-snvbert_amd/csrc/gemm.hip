@@ -224,15 +224,14 @@ extern "C" int snvrag_linear_ex(int dtype_in, int dtype_out, int64_t M, int64_t 
                                 int64_t ldc, const snvrag_epilogue_t* epi, const snvrag_rownorm_t* anorm,
                                 void* stream) {
   SNV_CHECK_ARG(M >= 0 && N > 0 && K > 0, "bad shape");
-  SNV_CHECK_ARG(A && W && C, "null pointer");
+  SNV_CHECK_PTRS(A, W, C);
   SNV_CHECK_ARG(dtype_in == SNVRAG_F32 || dtype_in == SNVRAG_BF16, "dtype_in");
   SNV_CHECK_ARG(dtype_out == SNVRAG_F32 || dtype_out == SNVRAG_BF16, "dtype_out");
   const int ein = dtype_in == SNVRAG_BF16 ? 8 : 4, eout = dtype_out == SNVRAG_BF16 ? 8 : 4;
   SNV_CHECK_ARG(K % 8 == 0, "K must be a multiple of 8");
   SNV_CHECK_ARG(lda % ein == 0 && ldw % ein == 0, "lda/ldw must keep 16-byte row alignment");
   SNV_CHECK_ARG(N % eout == 0 && ldc % eout == 0, "N/ldc must keep 16-byte output chunks");
-  SNV_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)C % 16) == 0,
-                "A/W/C must be 16-byte aligned");
+  SNV_CHECK_ALIGN(16, "A/W/C must be 16-byte aligned", A, W, C);
   if (M == 0) return 0;
   const int ept = dtype_in == SNVRAG_BF16 ? 64 : 32;
   const bool fused = anorm || (epi && (epi->ln_g || epi->stats_out));
@@ -253,7 +252,7 @@ extern "C" int snvrag_linear_ex(int dtype_in, int dtype_out, int64_t M, int64_t 
     e.resid = epi->resid; e.ld_resid = epi->ld_resid;
     SNV_CHECK_ARG(!e.row1 || e.col1, "row1 without col1");
     SNV_CHECK_ARG(!e.row2 || e.col2, "row2 without col2");
-    if (e.resid) SNV_CHECK_ARG(e.ld_resid % eout == 0 && ((uintptr_t)e.resid % 16) == 0, "resid alignment");
+    if (e.resid) SNV_CHECK_ARG(e.ld_resid % eout == 0 && aligned(16, e.resid), "resid alignment");
   }
   hipStream_t s = as_stream(stream);
   if (dtype_in == SNVRAG_BF16 && dtype_out == SNVRAG_BF16)

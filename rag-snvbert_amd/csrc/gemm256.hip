@@ -605,10 +605,7 @@ static int g3_launch(G2Args a, hipStream_t s) {
   // + bias table (+ EPI 1: LN g, be tables and the [4][G][32] row-sum exchange)
   constexpr size_t lds = (size_t)G3_NS * g3_img(G) + 384 * 4 + (EPI == 1 ? 2 * 384 * 4 + 4 * G * 32 * 4 : 0);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, 32 * G)), dim3(256), lds, s, a);
-  SNV_LAUNCH_CHECK();
-  return 0;
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)cdiv(a.M, 32 * G)), dim3(256), lds, s, a);
 }
 
 template <int VAR, int EPI = 0>
@@ -626,13 +623,7 @@ static int g3_dispatch(int G, const G2Args& a, hipStream_t s) {
 // of 32); past one round of 8-group workgroups, the G whose rounds x (G + 1) (a workgroup's time
 // ~ G plus a fixed prologue / epilogue share) is least; option g2_groups overrides
 static int g3_groups(long M) {
-  static int n_cu = 0;
-  if (n_cu <= 0) {
-    int dev = 0, v = 0;
-    n_cu = hipGetDevice(&dev) == hipSuccess &&
-                   hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0
-               ? v : 256;
-  }
+  const int n_cu = cu_count();
   int G = (int)std::min<long>(8, std::max<long>(4, (M + 32L * n_cu - 1) / (32L * n_cu)));
   if (M > 8L * 32 * n_cu) {
     long best = -1;
@@ -659,10 +650,7 @@ static int g2_launch(const G2Args& a, hipStream_t s) {
   auto kern = g2_kernel<NT, VAR>;
   constexpr size_t lds = (size_t)G2_NSLOT * SLAB_BYTES + 32 * NT * 4;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, G2_ROWS)), dim3(256), lds, s, a);
-  SNV_LAUNCH_CHECK();
-  return 0;
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)cdiv(a.M, G2_ROWS)), dim3(256), lds, s, a);
 }
 
 }  // namespace snvrag
@@ -689,13 +677,11 @@ extern "C" int snvrag_gemm256_forward(int64_t M, int N, int K, const void* A, in
                                       void* stream) {
   SNV_CHECK_ARG(N == 384, "gemm256: N = 384");
   SNV_CHECK_ARG(K >= 64 && K % 64 == 0, "gemm256: K % 64 == 0");
-  SNV_CHECK_ARG(A && wpacked && out, "null pointer");
+  SNV_CHECK_PTRS(A, wpacked, out);
   SNV_CHECK_ARG(M < (1L << 31), "bad M");              // (G2Args carries M as int)
   SNV_CHECK_ARG(M >= 0 && lda >= K && ldo >= N && (!resid || ld_resid >= N), "bad shape / leading dims");
   SNV_CHECK_ARG(lda % 8 == 0 && ldo % 8 == 0 && (!resid || ld_resid % 8 == 0), "16-byte rows");
-  SNV_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)wpacked % 16) == 0 &&
-                    ((uintptr_t)resid % 16) == 0,
-                "16-byte aligned operands");
+  SNV_CHECK_ALIGN(16, "16-byte aligned operands", A, out, wpacked, resid);
   SNV_CHECK_ARG(257L * lda * 2 < (1L << 31) && 257L * ldo * 2 < (1L << 31) &&
                     (!resid || 257L * ld_resid * 2 < (1L << 31)),
                 "row offsets must fit 31 bits");
@@ -732,14 +718,12 @@ extern "C" int snvrag_gemm256_ln_forward(int64_t M, int N, int K, const void* A,
                                          int64_t post_af_period, void* out, int64_t ldo, void* stream) {
   SNV_CHECK_ARG(N == 384, "gemm256: N = 384");
   SNV_CHECK_ARG(K >= 64 && K % 64 == 0, "gemm256: K % 64 == 0");
-  SNV_CHECK_ARG(A && wpacked && out && ln_g && ln_b, "null pointer");
+  SNV_CHECK_PTRS(A, wpacked, out, ln_g, ln_b);
   SNV_CHECK_ARG(M < (1L << 31), "bad M");
   SNV_CHECK_ARG(M >= 0 && lda >= K && ldo >= N && (!base || ld_base >= N), "bad shape / leading dims");
   SNV_CHECK_ARG(post_af_period >= 0, "bad af period");
   SNV_CHECK_ARG(lda % 8 == 0 && ldo % 8 == 0 && (!base || ld_base % 8 == 0), "16-byte rows");
-  SNV_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)wpacked % 16) == 0 &&
-                    ((uintptr_t)base % 16) == 0,
-                "16-byte aligned operands");
+  SNV_CHECK_ALIGN(16, "16-byte aligned operands", A, out, wpacked, base);
   SNV_CHECK_ARG(257L * lda * 2 < (1L << 31) && 257L * ldo * 2 < (1L << 31) &&
                     (!base || 257L * ld_base * 2 < (1L << 31)),
                 "row offsets must fit 31 bits");

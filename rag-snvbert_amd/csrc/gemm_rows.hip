@@ -355,15 +355,8 @@ static int launch_rows_v(long M, long N, long K, const void* A, long lda, const 
   SNV_CHECK_ARG(nb < (1L << 31), "grid too large");
   const size_t lds = NST * (size_t)(R_BM + BN) * ROWB + R_BM * sizeof(float2) + 6 * BN * sizeof(float);
   auto kern = rows_gemm_kernel<TI, TO, NW, RN>;
-  static bool attr = false;
-  if (!attr) {
-    SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(512), lds, s, (int)M, (int)N, (int)K, (const TI*)A, lda,
-                     (const TI*)W, ldw, (TO*)C, ldc, e, rn, tn);
-  SNV_LAUNCH_CHECK();
-  return 0;
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)nb), dim3(512), lds, s, (int)M, (int)N, (int)K, (const TI*)A, lda,
+                        (const TI*)W, ldw, (TO*)C, ldc, e, rn, tn);
 }
 
 template <typename TI, typename TO, int NW>

@@ -170,8 +170,8 @@ extern "C" int snvrag_bgzf_inflate(const uint8_t* comp, int64_t comp_bytes, cons
   SNV_CHECK_ARG(n_blocks >= 0 && n_blocks < (1LL << 31), "n_blocks must be in [0, 2^31)");
   SNV_CHECK_ARG(comp_bytes >= 0 && text_bytes >= 0, "comp_bytes and text_bytes must not be negative");
   if (n_blocks == 0) return 0;
-  SNV_CHECK_ARG(comp && table_host && table_dev && text && status, "null pointer");
-  SNV_CHECK_ARG(((uintptr_t)table_dev % 8) == 0, "table_dev must be 8-byte aligned");
+  SNV_CHECK_PTRS(comp, table_host, table_dev, text, status);
+  SNV_CHECK_ALIGN(8, "table_dev must be 8-byte aligned", table_dev);
   for (int64_t b = 0; b < n_blocks; ++b) {
     const int64_t in_off = table_host[4 * b], out_off = table_host[4 * b + 1], w2 = table_host[4 * b + 2];
     const int64_t in_len = (int32_t)(uint32_t)w2, isize = (int32_t)(uint32_t)((uint64_t)w2 >> 32);
@@ -190,9 +190,9 @@ extern "C" int snvrag_bgzf_inflate(const uint8_t* comp, int64_t comp_bytes, cons
 }
 
 extern "C" int snvrag_text_last_newline(const uint8_t* text, int64_t nbytes, int64_t* out, void* stream) {
-  SNV_CHECK_ARG(text && out, "null pointer");
+  SNV_CHECK_PTRS(text, out);
   SNV_CHECK_ARG(nbytes >= 0 && nbytes < (1LL << 40), "nbytes must be in [0, 2^40)");
-  SNV_CHECK_ARG(((uintptr_t)text % 16) == 0 && ((uintptr_t)out % 8) == 0, "text must be 16-byte, out 8-byte aligned");
+  SNV_CHECK_ARG(aligned(16, text) && aligned(8, out), "text must be 16-byte, out 8-byte aligned");
   hipLaunchKernelGGL(text_last_newline_kernel, dim3(1), dim3(LN_THREADS), 0, as_stream(stream), text, (long)nbytes, out);
   SNV_LAUNCH_CHECK();
   return 0;

@@ -934,7 +934,7 @@ __global__ __launch_bounds__(512) void scan2_kernel(const uint8_t* __restrict__ 
 }
 
 template <int KS, int LB>
-static void launch_scan2(int n_parts, int nq, hipStream_t s, const uint8_t* codes, long n_ref, long ld,
+static int launch_scan2(int n_parts, int nq, hipStream_t s, const uint8_t* codes, long n_ref, long ld,
                          const int8_t* lut, int k, long range, long off, uint64_t* parts, const int* th,
                          const int* wide) {
   constexpr size_t STAGE = (size_t)s2_rows(KS) * KS * 64;
@@ -946,14 +946,13 @@ static void launch_scan2(int n_parts, int nq, hipStream_t s, const uint8_t* code
     if (options().scan_mode == 1) kern = scan2_kernel<KS, LB, 1>;
     if (options().scan_mode == 2) kern = scan2_kernel<KS, LB, 2>;
   }
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int G = ((nq + 15) / 16 + 7) / 8;
   const long nwg = (long)((n_parts + 7) / 8) * 8 * G;
   // one query group: every code byte is read by exactly one workgroup, so stream it with
   // the non-temporal policy; with G > 1 the other groups read the range from L2 (default)
   const int nt = options().scan_nt >= 0 ? (int)(options().scan_nt != 0) : (G == 1);
-  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), lds, s, codes, n_ref, ld, lut, nq, k, range, off, parts, th,
-                     wide, n_parts, G, nt);
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)nwg), dim3(512), lds, s, codes, n_ref, ld, lut, nq, k, range, off, parts,
+                        th, wide, n_parts, G, nt);
 }
 
 // scan2_kernel over the bit-packed panel (bits[n_ref][ldb]): the same workgroup mapping and the
@@ -984,17 +983,16 @@ __global__ __launch_bounds__(512) void scan2_bits_kernel(const uint8_t* __restri
 
 // two expanded stages beside the candidate lists
 template <int KS, int LB>
-static void launch_scan2_bits(int n_parts, int nq, hipStream_t s, const uint8_t* bits, long n_ref, long ldb,
+static int launch_scan2_bits(int n_parts, int nq, hipStream_t s, const uint8_t* bits, long n_ref, long ldb,
                               const int8_t* lut, int k, long range, long off, uint64_t* parts, const int* th,
                               const int* wide) {
   constexpr size_t lds = 2 * (size_t)s2_rows(KS) * KS * 64 + S2_CAND;
   static_assert(lds <= S2_LDS, "LDS budget");
   auto kern = scan2_bits_kernel<KS, LB>;
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int G = ((nq + 15) / 16 + 7) / 8;
   const long nwg = (long)((n_parts + 7) / 8) * 8 * G;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(512), lds, s, bits, n_ref, ldb, lut, nq, k, range, off, parts, th,
-                     wide, n_parts, G);
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)nwg), dim3(512), lds, s, bits, n_ref, ldb, lut, nq, k, range, off, parts,
+                        th, wide, n_parts, G);
 }
 
 static int scan_parts(long n_ref, int nq) {
@@ -1057,7 +1055,7 @@ extern "C" int snvrag_knn_lut_panel(int64_t nq, int64_t L, int64_t D, const int6
                                     const uint8_t* site_mask, int32_t n_sites, int32_t n_sites_pad, int tok0,
                                     int tok1, int mask_tok, int limbs, void* lut_out, int32_t* exp_out,
                                     float* const_out, void* stream) {
-  SNV_CHECK_ARG(tok_q && W && Wp && site_mask && lut_out && exp_out, "null pointer");
+  SNV_CHECK_PTRS(tok_q, W, Wp, site_mask, lut_out, exp_out);
   SNV_CHECK_ARG(limbs == 1 || limbs == 2, "limbs must be 1 or 2");
   SNV_CHECK_ARG(n_sites_pad % 64 == 0 && n_sites_pad >= n_sites && n_sites + 2 <= L, "site padding");
   SNV_CHECK_ARG(n_sites_pad <= 20 * 64, "window longer than 1280 sites");
@@ -1071,8 +1069,7 @@ extern "C" int snvrag_knn_lut_panel(int64_t nq, int64_t L, int64_t D, const int6
   float* gdelta = (float*)((char*)lut_out + lut_ws_offset(nq, n_sites_pad, limbs));
   float* gcpart = gdelta + (size_t)nq * n_sites_pad;
   if (Aq || Ar) {
-    auto a16 = [](const void* p) { return p == nullptr || ((uintptr_t)p % 16) == 0; };
-    SNV_CHECK_ARG(D % 4 == 0 && a16(W) && a16(Wp) && a16(Aq) && a16(Ar),
+    SNV_CHECK_ARG(D % 4 == 0 && aligned(16, W, Wp, Aq, Ar),
                   "offset LUT: D % 4 == 0 and 16-byte aligned W / Wp / Aq / Ar (float4 rows)");
     const int64_t nch = std::min<int64_t>((L + LUT_CH - 1) / LUT_CH, lut_nch_max(n_sites_pad));
     hipLaunchKernelGGL(lut_delta_kernel, dim3((unsigned)nch, (unsigned)nq), dim3(256), 0, s,
@@ -1109,40 +1106,55 @@ extern "C" int snvrag_knn_threshold(const uint64_t* keys, int32_t nq, int k, int
 
 extern "C" int snvrag_knn_scan_parts(int64_t n_ref, int32_t nq) { return scan_parts(n_ref, nq); }
 
-extern "C" int snvrag_knn_scan(const uint8_t* codes, int64_t n_ref, int64_t ld_codes, int32_t n_sites_pad,
-                               const void* lut, int32_t nq, int limbs, int k, int64_t ref_offset,
-                               uint64_t* part_keys, int32_t n_parts, const int32_t* th_init, void* stream) {
-  SNV_CHECK_ARG(codes && lut && part_keys, "null pointer");
-  SNV_CHECK_ARG(k >= 1 && k <= 32, "k must be in [1, 32]");
-  SNV_CHECK_ARG(limbs == 1 || limbs == 2, "limbs");
-  SNV_CHECK_ARG(n_sites_pad % 64 == 0 && ld_codes >= n_sites_pad &&
-                    n_sites_pad <= (n_sites_pad % 256 == 0 ? 20 * 64 : 17 * 64), "site padding");
-  SNV_CHECK_ARG(ld_codes % 16 == 0 && ((uintptr_t)codes % 16) == 0, "codes must be 16-byte aligned rows");
-  SNV_CHECK_ARG(n_parts >= 1, "n_parts");
-  SNV_CHECK_ARG(n_ref + ref_offset < (1LL << 32), "panel index must fit 32 bits");
-  if (nq == 0) return 0;
+// what the two scan entries share: the five argument checks (reported under the entry's name) ...
+static int scan_check(const char* entry, const void* panel, const void* lut, const uint64_t* part_keys, int limbs,
+                      int k, int64_t n_ref, int64_t ref_offset, int32_t n_parts) {
+  SNV_CHECK_AS(entry, non_null(panel, lut, part_keys), "null pointer");
+  SNV_CHECK_AS(entry, k >= 1 && k <= 32, "k must be in [1, 32]");
+  SNV_CHECK_AS(entry, limbs == 1 || limbs == 2, "limbs");
+  SNV_CHECK_AS(entry, n_parts >= 1, "n_parts");
+  SNV_CHECK_AS(entry, n_ref + ref_offset < (1LL << 32), "panel index must fit 32 bits");
+  return 0;
+}
+// ... and the plan: refs per range (a multiple of 16, at least 16) and lut_kernel's "some query
+// needs two limbs" flag (limbs == 2 buffers only; null: every query runs the limbs it was given)
+struct ScanPlan { long range; const int* wide; };
+static ScanPlan scan_plan(int64_t n_ref, int32_t n_parts, int32_t nq, int32_t n_sites_pad, int limbs, const void* lut) {
   long range = (n_ref + n_parts - 1) / n_parts;
   range = ((range + 15) / 16) * 16;
   if (range == 0) range = 16;
+  const int* wide = (limbs == 2 && !options().knn_no_reduce)
+                        ? reinterpret_cast<const int*>((const int8_t*)lut + lut_tail_offset(nq, n_sites_pad) +
+                                                       (size_t)((nq + 15) / 16) * 16 * 4)
+                        : nullptr;
+  return {range, wide};
+}
+
+extern "C" int snvrag_knn_scan(const uint8_t* codes, int64_t n_ref, int64_t ld_codes, int32_t n_sites_pad,
+                               const void* lut, int32_t nq, int limbs, int k, int64_t ref_offset,
+                               uint64_t* part_keys, int32_t n_parts, const int32_t* th_init, void* stream) {
+  if (int rc = scan_check(__func__, codes, lut, part_keys, limbs, k, n_ref, ref_offset, n_parts)) return rc;
+  SNV_CHECK_ARG(n_sites_pad % 64 == 0 && ld_codes >= n_sites_pad &&
+                    n_sites_pad <= (n_sites_pad % 256 == 0 ? 20 * 64 : 17 * 64), "site padding");
+  SNV_CHECK_ARG(ld_codes % 16 == 0 && aligned(16, codes), "codes must be 16-byte aligned rows");
+  if (nq == 0) return 0;
+  const auto [range, wide] = scan_plan(n_ref, n_parts, nq, n_sites_pad, limbs, lut);
   const int KS = n_sites_pad / 64;
   dim3 g((unsigned)n_parts, (unsigned)(((nq + 15) / 16 + 3) / 4));
   hipStream_t s = as_stream(stream);
   const int8_t* L8 = (const int8_t*)lut;
-  // lut_kernel's "some query needs two limbs" flag (limbs == 2 buffers only)
-  const int* wide = (limbs == 2 && !options().knn_no_reduce)
-                        ? reinterpret_cast<const int*>(L8 + lut_tail_offset(nq, n_sites_pad) +
-                                                       (size_t)((nq + 15) / 16) * 16 * 4)
-                        : nullptr;
   evlog_begin(s);
   const bool v2 = n_sites_pad % 256 == 0 && n_sites_pad <= 1280;
   if (v2) {
+    int rc = 0;
 #define SCAN2(K_)                                                                                          \
   case K_:                                                                                                 \
-    if (limbs == 2) launch_scan2<K_, 2>(n_parts, nq, s, codes, n_ref, ld_codes, L8, k, range, ref_offset, part_keys, th_init, wide); \
-    else launch_scan2<K_, 1>(n_parts, nq, s, codes, n_ref, ld_codes, L8, k, range, ref_offset, part_keys, th_init, nullptr);          \
+    rc = limbs == 2 ? launch_scan2<K_, 2>(n_parts, nq, s, codes, n_ref, ld_codes, L8, k, range, ref_offset, part_keys, th_init, wide) \
+                    : launch_scan2<K_, 1>(n_parts, nq, s, codes, n_ref, ld_codes, L8, k, range, ref_offset, part_keys, th_init, nullptr); \
     break;
     switch (KS) { SCAN2(4) SCAN2(8) SCAN2(12) SCAN2(16) SCAN2(20) }
 #undef SCAN2
+    if (rc) return rc;
   } else {
 #define SCAN(KSM)                                                                                   \
   do {                                                                                              \
@@ -1154,8 +1166,8 @@ extern "C" int snvrag_knn_scan(const uint8_t* codes, int64_t n_ref, int64_t ld_c
   else if (KS <= 16) SCAN(16);
   else SCAN(17);
 #undef SCAN
+    SNV_LAUNCH_CHECK();
   }
-  SNV_LAUNCH_CHECK();
   // algorithmic bytes: every code byte of the window once + LUT + partial lists
   evlog_end(s, EV_KNN_SCAN, (double)n_ref * n_sites_pad + (double)nq * n_sites_pad * limbs +
                             (double)n_parts * nq * k * 8.0);
@@ -1166,33 +1178,24 @@ extern "C" int snvrag_knn_scan(const uint8_t* codes, int64_t n_ref, int64_t ld_c
 extern "C" int snvrag_knn_scan_bits(const uint8_t* bits, int64_t n_ref, int64_t ld_bits, int32_t n_sites_pad,
                                     const void* lut, int32_t nq, int limbs, int k, int64_t ref_offset,
                                     uint64_t* part_keys, int32_t n_parts, const int32_t* th_init, void* stream) {
-  SNV_CHECK_ARG(bits && lut && part_keys, "null pointer");
-  SNV_CHECK_ARG(k >= 1 && k <= 32, "k must be in [1, 32]");
-  SNV_CHECK_ARG(limbs == 1 || limbs == 2, "limbs");
+  if (int rc = scan_check(__func__, bits, lut, part_keys, limbs, k, n_ref, ref_offset, n_parts)) return rc;
   SNV_CHECK_ARG(n_sites_pad >= 256 && n_sites_pad % 256 == 0 && n_sites_pad <= 1280 && ld_bits * 8 >= n_sites_pad,
                 "site padding: n_sites_pad a multiple of 256 up to 1280, ld_bits >= n_sites_pad / 8");
-  SNV_CHECK_ARG(ld_bits % 8 == 0 && ((uintptr_t)bits % 8) == 0, "bit rows must be 8-byte aligned");
-  SNV_CHECK_ARG(n_parts >= 1, "n_parts");
-  SNV_CHECK_ARG(n_ref + ref_offset < (1LL << 32), "panel index must fit 32 bits");
+  SNV_CHECK_ARG(ld_bits % 8 == 0 && aligned(8, bits), "bit rows must be 8-byte aligned");
   if (nq == 0) return 0;
-  long range = (n_ref + n_parts - 1) / n_parts;
-  range = ((range + 15) / 16) * 16;
-  if (range == 0) range = 16;
+  const auto [range, wide] = scan_plan(n_ref, n_parts, nq, n_sites_pad, limbs, lut);
   hipStream_t s = as_stream(stream);
   const int8_t* L8 = (const int8_t*)lut;
-  const int* wide = (limbs == 2 && !options().knn_no_reduce)
-                        ? reinterpret_cast<const int*>(L8 + lut_tail_offset(nq, n_sites_pad) +
-                                                       (size_t)((nq + 15) / 16) * 16 * 4)
-                        : nullptr;
   evlog_begin(s);
+  int rc = 0;
 #define SCAN2B(K_)                                                                                          \
   case K_:                                                                                                  \
-    if (limbs == 2) launch_scan2_bits<K_, 2>(n_parts, nq, s, bits, n_ref, ld_bits, L8, k, range, ref_offset, part_keys, th_init, wide); \
-    else launch_scan2_bits<K_, 1>(n_parts, nq, s, bits, n_ref, ld_bits, L8, k, range, ref_offset, part_keys, th_init, nullptr);          \
+    rc = limbs == 2 ? launch_scan2_bits<K_, 2>(n_parts, nq, s, bits, n_ref, ld_bits, L8, k, range, ref_offset, part_keys, th_init, wide) \
+                    : launch_scan2_bits<K_, 1>(n_parts, nq, s, bits, n_ref, ld_bits, L8, k, range, ref_offset, part_keys, th_init, nullptr); \
     break;
   switch (n_sites_pad / 64) { SCAN2B(4) SCAN2B(8) SCAN2B(12) SCAN2B(16) SCAN2B(20) }
 #undef SCAN2B
-  SNV_LAUNCH_CHECK();
+  if (rc) return rc;
   // algorithmic bytes: every panel BIT of the window once + LUT + partial lists
   evlog_end(s, EV_KNN_SCAN, (double)n_ref * n_sites_pad / 8.0 + (double)nq * n_sites_pad * limbs +
                             (double)n_parts * nq * k * 8.0);
@@ -1213,7 +1216,7 @@ extern "C" size_t snvrag_topk_merge_ws_bytes(int32_t n_lists, int32_t nq, int k)
 
 extern "C" int snvrag_topk_merge(const uint64_t* keys, int32_t n_lists, int32_t nq, int k, uint64_t* out_keys,
                                  void* ws, size_t ws_bytes, void* stream) {
-  SNV_CHECK_ARG(keys && out_keys, "null pointer");
+  SNV_CHECK_PTRS(keys, out_keys);
   SNV_CHECK_ARG(k >= 1 && k <= 1024, "k");
   if (nq == 0) return 0;
   hipStream_t s = as_stream(stream);
@@ -1256,7 +1259,7 @@ template <bool CNT, bool BITS = false>
 static int rag_mean_launch(int dtype_out, int64_t nq, int64_t L, int64_t D, int k, const int64_t* idx,
                            const uint8_t* codes, int64_t ld_codes, int32_t n_sites, const float* W, const float* pe,
                            const float* Ar, int tok0, int tok1, int sos, int eos, int pad, void* out, void* stream) {
-  SNV_CHECK_ARG(idx && codes && W && pe && out, "null pointer");
+  SNV_CHECK_PTRS(idx, codes, W, pe, out);
   SNV_CHECK_ARG(D % 8 == 0 && n_sites + 2 <= L, "shape");
   if (nq == 0) return 0;
   SNV_CHECK_ARG(k >= 1 && k <= RM_KMAX, "k must be in [1, 128]");
@@ -1302,8 +1305,7 @@ extern "C" int snvrag_neighbor_counts(int64_t nq, int k, const int64_t* idx, con
                                       int64_t row0, int64_t n_rows, uint8_t* counts, int64_t ld_out, void* stream) {
   SNV_CHECK_ARG(idx && counts && (codes || n_rows == 0), "null pointer");
   SNV_CHECK_ARG(k >= 1 && k <= RM_KMAX, "k must be in [1, 128]");
-  SNV_CHECK_ARG(ld % 16 == 0 && ld_out % 16 == 0 && ld_out >= ld && ((uintptr_t)counts % 16) == 0 &&
-                    ((uintptr_t)codes % 16) == 0,
+  SNV_CHECK_ARG(ld % 16 == 0 && ld_out % 16 == 0 && ld_out >= ld && aligned(16, counts, codes),
                 "rows must be 16-byte multiples, counts row >= codes row");
   if (nq == 0) return 0;
   const long work = nq * (ld_out / 16);
@@ -1318,8 +1320,7 @@ extern "C" int snvrag_neighbor_counts_bits(int64_t nq, int k, const int64_t* idx
                                            void* stream) {
   SNV_CHECK_ARG(idx && counts && (bits || n_rows == 0), "null pointer");
   SNV_CHECK_ARG(k >= 1 && k <= RM_KMAX, "k must be in [1, 128]");
-  SNV_CHECK_ARG(ld_bits % 2 == 0 && ld_out % 16 == 0 && ld_out >= 8 * ld_bits && ((uintptr_t)counts % 16) == 0 &&
-                    ((uintptr_t)bits % 2) == 0,
+  SNV_CHECK_ARG(ld_bits % 2 == 0 && ld_out % 16 == 0 && ld_out >= 8 * ld_bits && aligned(16, counts) && aligned(2, bits),
                 "bit rows must be 2-byte multiples, counts rows 16-byte multiples of at least 8 * ld_bits");
   if (nq == 0) return 0;
   const long work = nq * (ld_out / 16);
@@ -1331,8 +1332,7 @@ extern "C" int snvrag_neighbor_counts_bits(int64_t nq, int k, const int64_t* idx
 
 extern "C" int snvrag_panel_synth_bits(uint8_t* bits, int64_t row0, int64_t n_rows, int64_t ld_bits, int32_t n_sites,
                                        const float* af, uint64_t seed, void* stream) {
-  SNV_CHECK_ARG(bits && af && ld_bits % 2 == 0 && ld_bits * 8 >= n_sites && row0 >= 0 && ((uintptr_t)bits % 2) == 0,
-                "bad args");
+  SNV_CHECK_ARG(bits && af && ld_bits % 2 == 0 && ld_bits * 8 >= n_sites && row0 >= 0 && aligned(2, bits), "bad args");
   if (n_rows == 0) return 0;
   const long work = n_rows * (ld_bits / 2);
   const int grid = (int)std::min<long>(cdiv(work, 256), 65536);
@@ -1345,8 +1345,7 @@ extern "C" int snvrag_panel_synth_bits(uint8_t* bits, int64_t row0, int64_t n_ro
 extern "C" int snvrag_panel_pack_bits(const uint8_t* codes, int64_t n, int64_t ld, uint8_t* bits, int64_t ld_bits,
                                       void* stream) {
   SNV_CHECK_ARG((codes && bits) || n == 0, "null pointer");
-  SNV_CHECK_ARG(n >= 0 && ld % 16 == 0 && ld_bits % 2 == 0 && ld_bits * 8 >= ld && ((uintptr_t)codes % 16) == 0 &&
-                    ((uintptr_t)bits % 2) == 0,
+  SNV_CHECK_ARG(n >= 0 && ld % 16 == 0 && ld_bits % 2 == 0 && ld_bits * 8 >= ld && aligned(16, codes) && aligned(2, bits),
                 "codes rows must be 16-byte multiples, bit rows 2-byte multiples of at least ld / 8");
   if (n == 0) return 0;
   const long work = n * (ld_bits / 2);
@@ -1360,8 +1359,7 @@ extern "C" int snvrag_panel_pack_bits(const uint8_t* codes, int64_t n, int64_t l
 extern "C" int snvrag_panel_unpack_rows(const uint8_t* bits, int64_t n_ref, int64_t ld_bits, const int64_t* rows,
                                         int64_t n_rows, uint8_t* out, int64_t ld_out, void* stream) {
   SNV_CHECK_ARG(n_rows == 0 || (rows && out && (bits || n_ref == 0)), "null pointer");
-  SNV_CHECK_ARG(n_ref >= 0 && n_rows >= 0 && ld_bits % 2 == 0 && ld_out % 16 == 0 && ((uintptr_t)out % 16) == 0 &&
-                    ((uintptr_t)bits % 2) == 0,
+  SNV_CHECK_ARG(n_ref >= 0 && n_rows >= 0 && ld_bits % 2 == 0 && ld_out % 16 == 0 && aligned(16, out) && aligned(2, bits),
                 "bit rows must be 2-byte multiples, output rows 16-byte multiples");
   if (n_rows == 0) return 0;
   const long work = n_rows * (ld_out / 16);

@@ -175,9 +175,9 @@ extern "C" size_t snvrag_knn_emb_packed_bytes(int64_t N, int64_t K) {
 }
 
 extern "C" int snvrag_knn_emb_pack(const void* E, int64_t N, int64_t K, void* Et, void* stream) {
-  SNV_CHECK_ARG(E && Et, "null pointer");
+  SNV_CHECK_PTRS(E, Et);
   SNV_CHECK_ARG(N > 0 && K > 0 && K % KE_KB == 0, "K must be a positive multiple of 64");
-  SNV_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)Et % 16) == 0, "pointers must be 16-byte aligned");
+  SNV_CHECK_ALIGN(16, "pointers must be 16-byte aligned", E, Et);
   const long units = (long)snvrag_knn_emb_packed_bytes(N, K) / 16;
   hipLaunchKernelGGL(knn_emb_pack_kernel, dim3((unsigned)cdiv(units, 256)), dim3(256), 0, as_stream(stream),
                      (const bf16*)E, (long)N, (long)K, (bf16*)Et, units);
@@ -205,23 +205,22 @@ extern "C" int snvrag_knn_emb_splits(int64_t N, int64_t K, int Bq) {
 
 extern "C" int snvrag_knn_emb_scan(const void* E, int64_t N, int64_t K, const void* Q, int Bq, int splits, float* ws,
                                    void* stream) {
-  SNV_CHECK_ARG(E && Q && ws, "null pointer");
+  SNV_CHECK_PTRS(E, Q, ws);
   SNV_CHECK_ARG(N > 0 && K > 0 && K % KE_KB == 0, "K must be a positive multiple of 64");
   SNV_CHECK_ARG(Bq > 0 && Bq <= 128 && splits >= 1 && splits <= 256, "Bq in [1, 128], splits in [1, 256]");
-  SNV_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)Q % 16) == 0, "pointers must be 16-byte aligned");
+  SNV_CHECK_ALIGN(16, "pointers must be 16-byte aligned", E, Q);
   SNV_CHECK_ARG((long)Bq * K * 2 < (1L << 31), "query block must stay below 2 GiB (32-bit buffer offsets)");
   hipStream_t s = as_stream(stream);
   const int qt = (Bq + 31) / 32;
   const dim3 grid((unsigned)cdiv(N, 4 * 32 * KE_RT), (unsigned)splits);
   const size_t lds = (size_t)(KE_PF + 1) * qt * 4 * 1024;
   evlog_begin(s);
+  int rc = 0;
   switch (qt) {
 #define KE_CASE(T)                                                                                         \
   case T:                                                                                                  \
-    SNV_HIP(hipFuncSetAttribute((const void*)knn_emb_dot_kernel<KE_RT, T, KE_PF>,                         \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                    \
-    hipLaunchKernelGGL((knn_emb_dot_kernel<KE_RT, T, KE_PF>), grid, dim3(256), lds, s, (const bf16*)E,      \
-                       (long)N, (long)K, (const bf16*)Q, Bq, splits, ws);                                  \
+    rc = SNV_LAUNCH_LDS((knn_emb_dot_kernel<KE_RT, T, KE_PF>), grid, dim3(256), lds, s, (const bf16*)E,    \
+                        (long)N, (long)K, (const bf16*)Q, Bq, splits, ws);                                 \
     break;
     KE_CASE(1)
     KE_CASE(2)
@@ -229,7 +228,7 @@ extern "C" int snvrag_knn_emb_scan(const void* E, int64_t N, int64_t K, const vo
     KE_CASE(4)
 #undef KE_CASE
   }
-  SNV_LAUNCH_CHECK();
+  if (rc) return rc;
   evlog_end(s, EV_KNN_SCAN, (double)N * K * 2 + (double)Bq * K * 2);
   return 0;
 }

@@ -142,7 +142,7 @@ extern "C" int snvrag_layernorm(int dtype_in, int dtype_out, int64_t M, int64_t 
                                 int64_t ldx, const void* R, int64_t ldr, const float* gamma,
                                 const float* beta, float eps, void* Y, int64_t ldy,
                                 const snvrag_ln_post_t* post, void* stream) {
-  SNV_CHECK_ARG(X && Y && gamma && beta, "null pointer");
+  SNV_CHECK_PTRS(X, Y, gamma, beta);
   const int vi = dtype_in == SNVRAG_BF16 ? 8 : 4;
   SNV_CHECK_ARG(N % vi == 0 && N / vi <= 64 * LN_MAX_CHUNKS, "N unsupported (multiple of 16 B, <= 4096 bf16 / 2048 f32)");
   SNV_CHECK_ARG(ldx % vi == 0 && (!R || ldr % vi == 0), "ld alignment");
@@ -173,7 +173,7 @@ extern "C" int snvrag_layernorm(int dtype_in, int dtype_out, int64_t M, int64_t 
 extern "C" int snvrag_rag_weighted_concat(int dtype, int64_t M, int64_t D, const void* q,
                                           const void* rag, const void* wgt, int64_t period,
                                           void* out, void* stream) {
-  SNV_CHECK_ARG(q && rag && wgt && out, "null pointer");
+  SNV_CHECK_PTRS(q, rag, wgt, out);
   SNV_CHECK_ARG(D % 8 == 0, "D must be a multiple of 8");
   if (M == 0) return 0;
   hipStream_t s = as_stream(stream);

@@ -172,12 +172,11 @@ extern "C" int snvrag_site_stats(int64_t n, int64_t S, const float* h1, const fl
                                  const int8_t* truth, int64_t n_truth, int64_t S_truth, const int32_t* truth_row,
                                  const int32_t* truth_col, double* est, double* acc, int32_t* table,
                                  int32_t* bad_count, void* stream) {
-  SNV_CHECK_ARG(h1 && h2 && gt && est, "null pointer");
+  SNV_CHECK_PTRS(h1, h2, gt, est);
   SNV_CHECK_ARG(n >= 1 && n < (1LL << 31), "n must be in [1, 2^31)");
   SNV_CHECK_ARG(S >= 1 && S < (1LL << 31), "S must be in [1, 2^31)");
-  SNV_CHECK_ARG(((uintptr_t)gt % 16) == 0, "gt must be 16-byte aligned");
-  SNV_CHECK_ARG(((uintptr_t)h1 % 4) == 0 && ((uintptr_t)h2 % 4) == 0 && ((uintptr_t)est % 8) == 0,
-                "h1 / h2 must be 4-byte and est 8-byte aligned");
+  SNV_CHECK_ALIGN(16, "gt must be 16-byte aligned", gt);
+  SNV_CHECK_ARG(aligned(4, h1, h2) && aligned(8, est), "h1 / h2 must be 4-byte and est 8-byte aligned");
   const unsigned grid = (unsigned)cdiv(n, QS_WAVES);
   if (!truth) {
     hipLaunchKernelGGL(site_stats_kernel<false>, dim3(grid), dim3(64 * QS_WAVES), 0, as_stream(stream), (long)n, (int)S,
@@ -189,8 +188,7 @@ extern "C" int snvrag_site_stats(int64_t n, int64_t S, const float* h1, const fl
                 "truth needs truth_row, truth_col, acc, table and bad_count");
   SNV_CHECK_ARG(n_truth >= 1 && S_truth >= 1 && n_truth < (1LL << 31) && S_truth < (1LL << 31),
                 "n_truth and S_truth must be in [1, 2^31)");
-  SNV_CHECK_ARG(((uintptr_t)truth % 2) == 0 && ((uintptr_t)acc % 8) == 0 && ((uintptr_t)table % 4) == 0 &&
-                    ((uintptr_t)truth_row % 4) == 0 && ((uintptr_t)truth_col % 4) == 0 && ((uintptr_t)bad_count % 4) == 0,
+  SNV_CHECK_ARG(aligned(2, truth) && aligned(8, acc) && aligned(4, table, truth_row, truth_col, bad_count),
                 "misaligned truth, acc, table, truth_row, truth_col or bad_count");
   hipLaunchKernelGGL(site_stats_kernel<true>, dim3(grid), dim3(64 * QS_WAVES), 0, as_stream(stream), (long)n, (int)S, h1,
                      h2, gt, truth, (long)n_truth, (long)S_truth, truth_row, truth_col, est, acc, table, bad_count);

@@ -51,7 +51,7 @@ using namespace snvrag;
 
 extern "C" int snvrag_hamming_lists(int64_t nq, int64_t N, int32_t nw, int k, const uint32_t* codes_wm,
                                     const uint32_t* queries, uint64_t* lists, void* stream) {
-  SNV_CHECK_ARG(codes_wm && queries && lists, "null pointer");
+  SNV_CHECK_PTRS(codes_wm, queries, lists);
   SNV_CHECK_ARG(k >= 1 && k <= HL_KMAX, "k must be in [1, 32]");
   SNV_CHECK_ARG(nw >= 1 && nw <= 2048, "1 .. 2048 words (65536 genotype bits) per row");
   SNV_CHECK_ARG(N >= 0 && N < (1LL << 32), "row index must fit 32 bits");

@@ -667,10 +667,7 @@ static int mlp_launch(SgArgs a, hipStream_t s) {
   // (af_fusion: 1.465 vs 1.489 ms)
   a.desync = stagger_step(cdiv(a.M, 128), 4 * 256, options().mlp_desync, AFG ? 25000 : 5000);
   const size_t lds = (size_t)SG_NSLOT * SLAB_BYTES + SG_VEC_BYTES;
-  SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, 128)), dim3(256), lds, s, a);
-  SNV_LAUNCH_CHECK();
-  return 0;
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)cdiv(a.M, 128)), dim3(256), lds, s, a);
 }
 
 // One thread per 16-byte piece (8 bf16) of the stream, in sgemm_piece_src's order (mfma32.h)
@@ -732,10 +729,7 @@ static int sg_launch(SgArgs a, hipStream_t s) {
                           WAVES == 8 ? 10000 : EPI == SG_LN ? 5500 : 10000);
   const size_t lds = (size_t)SG_NSLOT * SLAB_BYTES + SG_VEC_BYTES;
   static_assert((size_t)SG_NSLOT * SLAB_BYTES + SG_VEC_BYTES <= 160 * 1024, "LDS budget");
-  SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, 32 * WAVES)), dim3(64 * WAVES), lds, s, a);
-  SNV_LAUNCH_CHECK();
-  return 0;
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)cdiv(a.M, 32 * WAVES)), dim3(64 * WAVES), lds, s, a);
 }
 
 template <int D>
@@ -778,7 +772,7 @@ extern "C" size_t snvrag_sgemm_pack_bytes(int D, int N) {
 
 extern "C" int snvrag_sgemm_pack(int D, int N, const void* w, void* out, void* stream) {
   SNV_CHECK_ARG(snvrag_sgemm_pack_bytes(D, N) > 0, "stream GEMM needs D in {128, 256, 384, 768} and N % 64 == 0");
-  SNV_CHECK_ARG(w && out, "null pointer");
+  SNV_CHECK_PTRS(w, out);
   const long pieces = (long)N * D / 8;
   hipLaunchKernelGGL(sg_pack_kernel, dim3((unsigned)cdiv(pieces, 256)), dim3(256), 0, as_stream(stream), D, pieces,
                      (const bf16*)w, (bf16*)out);
@@ -801,8 +795,8 @@ extern "C" int snvrag_sgemm_forward(int64_t M, int D, int N, int epi, int act, f
                                     void* stream) {
   SNV_CHECK_ARG(snvrag_sgemm_pack_bytes(D, N) > 0, "stream GEMM needs D in {128, 256, 384, 768} and N % 64 == 0");
   SNV_CHECK_ARG(epi == SG_ACT || epi == SG_HEAD2 || epi == SG_LN, "bad epilogue");
-  SNV_CHECK_ARG(x && wstream && vec, "null pointer");
-  SNV_CHECK_ARG(M >= 0 && M < (1L << 31), "bad M");
+  SNV_CHECK_PTRS(x, wstream, vec);
+  SNV_CHECK_M(M);
   const bool rank = r1 != nullptr;
   SNV_CHECK_ARG(!rank || (r2 && period > 0), "rank terms need r1, r2 and a period");
   SNV_CHECK_ARG(epi != SG_HEAD2 || (!rank && N == 4 * D && probs), "head epilogue: no rank terms, N = 4D, probs");
@@ -813,8 +807,7 @@ extern "C" int snvrag_sgemm_forward(int64_t M, int D, int N, int epi, int act, f
                         : (epi == SG_LN ? sg_nvec<SG_LN, false>(N)
                                         : epi == SG_HEAD2 ? sg_nvec<SG_HEAD2, false>(N) : sg_nvec<SG_ACT, false>(N));
   SNV_CHECK_ARG(nvec * 4 <= SG_VEC_BYTES, "vector table exceeds the LDS budget");
-  SNV_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)wstream % 16) == 0 && (!out || ((uintptr_t)out % 16) == 0),
-                "pointers must be 16-byte aligned");
+  SNV_CHECK_ALIGN(16, "pointers must be 16-byte aligned", x, wstream, out);
   if (M == 0) return 0;
   const SgArgs a{(int)M, N, (const bf16*)x, (bf16*)out, (const char*)wstream, vec, r1, r2, (int)period,
                  probs, logits, slope, eps, nullptr, nullptr, 0};
@@ -840,12 +833,10 @@ extern "C" int snvrag_sgemm_cat_forward(int64_t M, int Dh, int N, const void* q,
                                         int64_t period2, const void* wstream, const float* vec, void* out,
                                         void* stream) {
   SNV_CHECK_ARG(Dh == 384 && N > 0 && N % 64 == 0, "concatenated-input GEMM needs D/2 = 384 and N % 64 == 0");
-  SNV_CHECK_ARG(q && x2 && g2 && wstream && vec && out, "null pointer");
+  SNV_CHECK_PTRS(q, x2, g2, wstream, vec, out);
   SNV_CHECK_ARG(M >= 0 && M < (1L << 31) && period2 > 0 && M * N * 2 < (1L << 31), "bad M / period");
   SNV_CHECK_ARG(N * 4 <= SG_VEC_BYTES, "vector table exceeds the LDS budget");
-  SNV_CHECK_ARG(((uintptr_t)q % 16) == 0 && ((uintptr_t)x2 % 16) == 0 && ((uintptr_t)g2 % 16) == 0 &&
-                    ((uintptr_t)wstream % 16) == 0 && ((uintptr_t)out % 16) == 0,
-                "pointers must be 16-byte aligned");
+  SNV_CHECK_ALIGN(16, "pointers must be 16-byte aligned", q, x2, g2, wstream, out);
   if (M == 0) return 0;
   const SgArgs a{(int)M, N, (const bf16*)q, (bf16*)out, (const char*)wstream, vec, nullptr, nullptr, 0,
                  nullptr, nullptr, 0.f, 0.f, (const bf16*)x2, (const bf16*)g2, (int)period2};
@@ -863,7 +854,7 @@ extern "C" size_t snvrag_mlp_pack_bytes(int D) {
 
 extern "C" int snvrag_mlp_pack(int D, const void* w1, const void* w2, void* out, void* stream) {
   SNV_CHECK_ARG(snvrag_mlp_pack_bytes(D) > 0, "MLP stream needs D = 384");
-  SNV_CHECK_ARG(w1 && w2 && out, "null pointer");
+  SNV_CHECK_PTRS(w1, w2, out);
   const long pieces = (long)snvrag_mlp_pack_bytes(D) / 16;
   hipLaunchKernelGGL(mlp_pack_kernel, dim3((unsigned)cdiv(pieces, 256)), dim3(256), 0, as_stream(stream), D, pieces,
                      (const bf16*)w1, (const bf16*)w2, (bf16*)out);
@@ -876,12 +867,11 @@ extern "C" int snvrag_mlp_forward(int64_t M, int D, int epi2, const void* x, con
                                   void* stream) {
   SNV_CHECK_ARG(D == 384, "MLP kernel needs D = 384");
   SNV_CHECK_ARG(epi2 == 0 || epi2 == 1, "epi2: 0 sigmoid, 1 LayerNorm");
-  SNV_CHECK_ARG(x && wstream && vec && out, "null pointer");
-  SNV_CHECK_ARG(M >= 0 && M < (1L << 31), "bad M");
+  SNV_CHECK_PTRS(x, wstream, vec, out);
+  SNV_CHECK_M(M);
   const bool rank = r1 != nullptr;
   SNV_CHECK_ARG(!rank || (r2 && period > 0), "rank terms need r1, r2 and a period");
-  SNV_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)wstream % 16) == 0 && ((uintptr_t)out % 16) == 0,
-                "pointers must be 16-byte aligned");
+  SNV_CHECK_ALIGN(16, "pointers must be 16-byte aligned", x, wstream, out);
   if (M == 0) return 0;
   const SgArgs a{(int)M, D, (const bf16*)x, (bf16*)out, (const char*)wstream, vec, r1, r2, (int)period,
                  nullptr, nullptr, 0.f, eps, nullptr, nullptr, 0};
@@ -898,10 +888,9 @@ extern "C" int snvrag_mlp_afgate_forward(int64_t M, int D, const float* af, cons
                                          float res_scale, const void* wstream, const float* vec, void* out,
                                          void* stream) {
   SNV_CHECK_ARG(D == 384, "MLP kernel needs D = 384");
-  SNV_CHECK_ARG(af && af_p && gate_frags && wstream && vec && out, "null pointer");
-  SNV_CHECK_ARG(M >= 0 && M < (1L << 31), "bad M");
-  SNV_CHECK_ARG(((uintptr_t)gate_frags % 16) == 0 && ((uintptr_t)wstream % 16) == 0 && ((uintptr_t)out % 16) == 0,
-                "pointers must be 16-byte aligned");
+  SNV_CHECK_PTRS(af, af_p, gate_frags, wstream, vec, out);
+  SNV_CHECK_M(M);
+  SNV_CHECK_ALIGN(16, "pointers must be 16-byte aligned", gate_frags, wstream, out);
   SNV_CHECK_ARG((4 * D + D + AFG_TAB) * 4 <= SG_VEC_BYTES, "vector table exceeds the LDS budget");
   if (M == 0) return 0;
   const SgArgs a{(int)M, D, nullptr, (bf16*)out, (const char*)wstream, vec, af, af_p, (int)M,

@@ -1065,25 +1065,11 @@ static int launch_proj(const TailArgs& a, hipStream_t s) {
   auto kern = tail_kernel<D, false, TL_PF4, 0, true, NC>;
   constexpr size_t lds = (size_t)TL_NSLOT * SLAB_BYTES + NC * D * 4;
   static_assert(NC * D * 4 <= TL_VEC_LDS && lds <= 160 * 1024, "LDS budget");
-  SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, TL_ROWS)), dim3(256), lds, s, a);
-  SNV_LAUNCH_CHECK();
-  return 0;
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)cdiv(a.M, TL_ROWS)), dim3(256), lds, s, a);
 }
 
 static unsigned long long* g_tail_stamps = nullptr;   // snvrag_tail_stamps (diagnostics)
 unsigned long long* diag_stamps() { return g_tail_stamps; }
-
-static int cu_count() {
-  static int n[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  if (n[dev] <= 0) {
-    int v = 0;
-    n[dev] = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 256;
-  }
-  return n[dev];
-}
 
 template <int D>
 static int launch_tailp(TailArgs a, hipStream_t s) {
@@ -1097,10 +1083,7 @@ static int launch_tailp(TailArgs a, hipStream_t s) {
     kern = tailp_kernel<D, true>;
     a.stamps = g_tail_stamps;
   }
-  SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, s, a);
-  SNV_LAUNCH_CHECK();
-  return 0;
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)grid), dim3(256), lds, s, a);
 }
 
 // the wide-row tail's first-round stagger (launch_tail below and snvrag_tail_qkv_forward)
@@ -1140,21 +1123,13 @@ static int launch_tail(TailArgs a, hipStream_t s) {
   a.desync = stagger_step(cdiv(a.M, TL_ROWS), 8 * 256, options().tail_desync, 25000 * D / 384 * D / 384);
   constexpr size_t lds = (size_t)TL_NSLOT * SLAB_BYTES + 7 * D * 4;     // ring + b1, g1, be1, b_o
   static_assert(7 * D * 4 <= TL_VEC_LDS && lds <= 160 * 1024, "LDS budget");
-  SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, TL_ROWS)), dim3(256), lds, s, a);
-  SNV_LAUNCH_CHECK();
-  return 0;
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)cdiv(a.M, TL_ROWS)), dim3(256), lds, s, a);
 }
 
 static bool tail_d_ok(int D) { return D == 128 || D == 256 || D == 384; }
 
 static size_t tail_bytes(int D) {
-  switch (D) {
-    case 128: return (size_t)TailShape<128>::NSLAB * SLAB_BYTES;
-    case 256: return (size_t)TailShape<256>::NSLAB * SLAB_BYTES;
-    case 384: return (size_t)TailShape<384>::NSLAB * SLAB_BYTES;
-    default: return 0;
-  }
+  return !tail_d_ok(D) ? 0 : dispatch_d(D, [](auto d) { return (size_t)TailShape<d()>::NSLAB * SLAB_BYTES; });
 }
 
 }  // namespace snvrag
@@ -1170,7 +1145,7 @@ extern "C" int snvrag_tail_stamps(void* buf) {
 
 extern "C" int snvrag_tail_pack(int D, const void* w_o, const void* w1, const void* w2g, void* out, void* stream) {
   SNV_CHECK_ARG(tail_d_ok(D), "block tail needs D in {128, 256, 384}");
-  SNV_CHECK_ARG(w_o && w1 && w2g && out, "null pointer");
+  SNV_CHECK_PTRS(w_o, w1, w2g, out);
   const long pieces = (long)(tail_bytes(D) / 16);
   hipLaunchKernelGGL(tail_pack_kernel, dim3((unsigned)cdiv(pieces, 256)), dim3(256), 0, as_stream(stream), D, pieces,
                      (const bf16*)w_o, (const bf16*)w1, (const bf16*)w2g, (bf16*)out);
@@ -1181,20 +1156,8 @@ extern "C" int snvrag_tail_pack(int D, const void* w_o, const void* w1, const vo
 static int tail_common(int64_t M, int D, bool pre, const TailArgs& a, void* stream) {
   hipStream_t s = as_stream(stream);
   evlog_begin(s);
-  int rc;
-  if (pre) {
-    switch (D) {
-      case 128: rc = launch_tail<128, true>(a, s); break;
-      case 256: rc = launch_tail<256, true>(a, s); break;
-      default: rc = launch_tail<384, true>(a, s); break;
-    }
-  } else {
-    switch (D) {
-      case 128: rc = launch_tail<128, false>(a, s); break;
-      case 256: rc = launch_tail<256, false>(a, s); break;
-      default: rc = launch_tail<384, false>(a, s); break;
-    }
-  }
+  const int rc = pre ? dispatch_d(D, [&](auto d) { return launch_tail<d(), true>(a, s); })
+                     : dispatch_d(D, [&](auto d) { return launch_tail<d(), false>(a, s); });
   if (rc) return rc;
   evlog_end(s, EV_BLOCK, 2.0 * M * (double)D * D * (pre ? 9 : 8));
   return 0;
@@ -1204,12 +1167,10 @@ extern "C" int snvrag_tail_forward(int64_t M, int D, const void* att, void* x, c
                                    const float* ln1_g, const float* ln1_b, const float* ffn_vec, float eps,
                                    void* stream) {
   SNV_CHECK_ARG(tail_d_ok(D), "block tail needs D in {128, 256, 384}");
-  SNV_CHECK_ARG(att && x && wstream && b_o && ln1_g && ln1_b && ffn_vec, "null pointer");
+  SNV_CHECK_PTRS(att, x, wstream, b_o, ln1_g, ln1_b, ffn_vec);
   SNV_CHECK_ARG(att != x, "att and x must not alias");
-  SNV_CHECK_ARG(M >= 0 && M < (1L << 31), "bad M");
-  SNV_CHECK_ARG(((uintptr_t)att % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)wstream % 16) == 0 &&
-                    ((uintptr_t)ffn_vec % 16) == 0,
-                "pointers must be 16-byte aligned");
+  SNV_CHECK_M(M);
+  SNV_CHECK_ALIGN(16, "pointers must be 16-byte aligned", att, x, wstream, ffn_vec);
   if (M == 0) return 0;
   const TailArgs a{(int)M, (const bf16*)att, (const bf16*)x, (bf16*)x, (const char*)wstream, ffn_vec, b_o, ln1_g,
                    ln1_b, eps, nullptr, 0};
@@ -1224,14 +1185,11 @@ extern "C" int snvrag_tail_qkv_forward(int64_t M, int D, const void* att, void* 
   SNV_CHECK_ARG(D == 384, "the fused tail + QKV needs D = 384");
   SNV_CHECK_ARG(options().tail_variant == 0 && (options().tail_wide == 1 || options().tail_wide == 2),
                 "the fused tail + QKV runs on the wide-row tail only (tail_wide 1 / 2, tail_variant 0)");
-  SNV_CHECK_ARG(att && x && wstream && b_o && ln1_g && ln1_b && ffn_vec && qkv_pw && b_qkv && qkv_out, "null pointer");
+  SNV_CHECK_PTRS(att, x, wstream, b_o, ln1_g, ln1_b, ffn_vec, qkv_pw, b_qkv, qkv_out);
   SNV_CHECK_ARG(att != x && qkv_out != x && qkv_out != att, "att, x and qkv_out must not alias");
-  SNV_CHECK_ARG(M >= 0 && M < (1L << 31), "bad M");
+  SNV_CHECK_M(M);
   SNV_CHECK_ARG((long)M * 3 * D * 2 < (1L << 31), "qkv_out past 2 GiB: run snvrag_tail_forward and a projection");
-  SNV_CHECK_ARG(((uintptr_t)att % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)wstream % 16) == 0 &&
-                    ((uintptr_t)ffn_vec % 16) == 0 && ((uintptr_t)qkv_pw % 16) == 0 && ((uintptr_t)b_qkv % 16) == 0 &&
-                    ((uintptr_t)qkv_out % 16) == 0,
-                "pointers must be 16-byte aligned");
+  SNV_CHECK_ALIGN(16, "pointers must be 16-byte aligned", att, x, wstream, ffn_vec, qkv_pw, b_qkv, qkv_out);
   if (M == 0) return 0;
   hipStream_t s = as_stream(stream);
   evlog_begin(s);
@@ -1245,12 +1203,10 @@ extern "C" int snvrag_tail_qkv_forward(int64_t M, int D, const void* att, void* 
 extern "C" int snvrag_tail_ffn_forward(int64_t M, int D, const void* x1, void* out, const void* wstream,
                                        const float* ffn_vec, float eps, void* stream) {
   SNV_CHECK_ARG(tail_d_ok(D), "block tail needs D in {128, 256, 384}");
-  SNV_CHECK_ARG(x1 && out && wstream && ffn_vec, "null pointer");
+  SNV_CHECK_PTRS(x1, out, wstream, ffn_vec);
   SNV_CHECK_ARG(x1 != out, "x1 and out must not alias");
-  SNV_CHECK_ARG(M >= 0 && M < (1L << 31), "bad M");
-  SNV_CHECK_ARG(((uintptr_t)x1 % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)wstream % 16) == 0 &&
-                    ((uintptr_t)ffn_vec % 16) == 0,
-                "pointers must be 16-byte aligned");
+  SNV_CHECK_M(M);
+  SNV_CHECK_ALIGN(16, "pointers must be 16-byte aligned", x1, out, wstream, ffn_vec);
   if (M == 0) return 0;
   const TailArgs a{(int)M, (const bf16*)x1, nullptr, (bf16*)out, (const char*)wstream, ffn_vec, nullptr, nullptr,
                    nullptr, eps, nullptr, 0};
@@ -1258,19 +1214,14 @@ extern "C" int snvrag_tail_ffn_forward(int64_t M, int D, const void* x1, void* o
 }
 
 static size_t proj_bytes(int D, int NC) {
-  switch (D) {
-    case 128: return (size_t)NC * TailShape<128>::NPRE * SLAB_BYTES;
-    case 256: return (size_t)NC * TailShape<256>::NPRE * SLAB_BYTES;
-    case 384: return (size_t)NC * TailShape<384>::NPRE * SLAB_BYTES;
-    default: return 0;
-  }
+  return !tail_d_ok(D) ? 0 : dispatch_d(D, [&](auto d) { return (size_t)NC * TailShape<d()>::NPRE * SLAB_BYTES; });
 }
 
 extern "C" size_t snvrag_proj_pack_bytes(int D, int NC) { return proj_bytes(D, NC); }
 
 extern "C" int snvrag_proj_pack(int D, int NC, const void* w, void* out, void* stream) {
   SNV_CHECK_ARG(tail_d_ok(D) && (NC == 1 || NC == 3), "projection needs D in {128, 256, 384}, NC in {1, 3}");
-  SNV_CHECK_ARG(w && out, "null pointer");
+  SNV_CHECK_PTRS(w, out);
   const long pieces = (long)(proj_bytes(D, NC) / 16);
   hipLaunchKernelGGL(proj_pack_kernel, dim3((unsigned)cdiv(pieces, 256)), dim3(256), 0, as_stream(stream), D, pieces,
                      (const bf16*)w, (bf16*)out);
@@ -1281,11 +1232,10 @@ extern "C" int snvrag_proj_pack(int D, int NC, const void* w, void* out, void* s
 extern "C" int snvrag_proj_forward(int64_t M, int D, int NC, const void* x, const void* wstream, const float* bias,
                                    void* out, void* stream) {
   SNV_CHECK_ARG(tail_d_ok(D) && (NC == 1 || NC == 3), "projection needs D in {128, 256, 384}, NC in {1, 3}");
-  SNV_CHECK_ARG(x && wstream && bias && out, "null pointer");
+  SNV_CHECK_PTRS(x, wstream, bias, out);
   SNV_CHECK_ARG(x != out, "x and out must not alias");
-  SNV_CHECK_ARG(M >= 0 && M < (1L << 31), "bad M");
-  SNV_CHECK_ARG(((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)wstream % 16) == 0,
-                "pointers must be 16-byte aligned");
+  SNV_CHECK_M(M);
+  SNV_CHECK_ALIGN(16, "pointers must be 16-byte aligned", x, out, wstream);
   if (M == 0) return 0;
   hipStream_t s = as_stream(stream);
   const TailArgs a{(int)M, (const bf16*)x, nullptr, (bf16*)out, (const char*)wstream, bias, nullptr, nullptr,
@@ -1296,17 +1246,8 @@ extern "C" int snvrag_proj_forward(int64_t M, int D, int NC, const void* x, cons
     // the wide-row projection (tailw.hip): first-round stagger as the block tail's
     const int desync = stagger_step(cdiv(M, TL_ROWS), 8 * 256, options().sg_desync, 8000);
     rc = projw_launch((int)M, NC, x, wstream, bias, out, desync, s);
-    if (rc) return rc;
-    evlog_end(s, EV_GEMM, 2.0 * M * (double)D * D * NC);
-    return 0;
-  }
-  switch (D * 8 + NC) {
-    case 128 * 8 + 1: rc = launch_proj<128, 1>(a, s); break;
-    case 128 * 8 + 3: rc = launch_proj<128, 3>(a, s); break;
-    case 256 * 8 + 1: rc = launch_proj<256, 1>(a, s); break;
-    case 256 * 8 + 3: rc = launch_proj<256, 3>(a, s); break;
-    case 384 * 8 + 1: rc = launch_proj<384, 1>(a, s); break;
-    default: rc = launch_proj<384, 3>(a, s); break;
+  } else {
+    rc = dispatch_d(D, [&](auto d) { return NC == 1 ? launch_proj<d(), 1>(a, s) : launch_proj<d(), 3>(a, s); });
   }
   if (rc) return rc;
   evlog_end(s, EV_GEMM, 2.0 * M * (double)D * D * NC);

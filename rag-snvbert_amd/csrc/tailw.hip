@@ -1016,10 +1016,7 @@ int tailw_launch(int M, const void* att, const void* resid, void* out, const voi
   auto kern = var == 1 ? tailw_kernel<1> : var == 2 ? tailw_kernel<2> : var == 4 ? tailw_kernel<4>
               : var == 8 ? tailw_kernel<8> : var == 9 ? tailw_kernel<9> : var == 16 ? tailw_kernel<16>
               : var == 17 ? tailw_kernel<17> : tailw_kernel<0>;
-  SNV_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS));
-  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), TW_LDS, s, a);
-  SNV_LAUNCH_CHECK();
-  return 0;
+  return SNV_LAUNCH_LDS(kern, dim3((unsigned)nwg), dim3(256), TW_LDS, s, a);
 }
 
 
@@ -1073,10 +1070,7 @@ void projw_kernel(PwArgs p) {
 
 int projw_launch(int M, int NC, const void* x, const void* ws, const float* bias, void* out, int desync, hipStream_t s) {
   PwArgs a{M, NC, (const bf16*)x, (const char*)ws, bias, (bf16*)out, desync};
-  SNV_HIP(hipFuncSetAttribute((const void*)projw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS));
-  hipLaunchKernelGGL(projw_kernel, dim3((unsigned)cdiv(M, 128)), dim3(256), TW_LDS, s, a);
-  SNV_LAUNCH_CHECK();
-  return 0;
+  return SNV_LAUNCH_LDS(projw_kernel, dim3((unsigned)cdiv(M, 128)), dim3(256), TW_LDS, s, a);
 }
 
 }  // namespace snvrag

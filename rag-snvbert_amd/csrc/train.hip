@@ -178,7 +178,7 @@ using namespace snvrag;
 
 extern "C" int snvrag_focal_loss(int64_t M, int C, const float* probs, const int64_t* labels, const uint8_t* mask,
                                  float gamma, float weight, float* loss_sum, float* grad, void* stream) {
-  SNV_CHECK_ARG(probs && labels && mask && loss_sum && grad, "null pointer");
+  SNV_CHECK_PTRS(probs, labels, mask, loss_sum, grad);
   SNV_CHECK_ARG(C >= 1 && C <= 4, "classes must be 1..4");
   if (M == 0) return 0;
   hipLaunchKernelGGL(focal_kernel<false>, dim3(cdiv(M, 256)), dim3(256), 0, as_stream(stream), (long)M, C, probs,
@@ -192,7 +192,7 @@ extern "C" size_t snvrag_focal_loss_det_ws_bytes(int64_t M) { return (size_t)cdi
 extern "C" int snvrag_focal_loss_det(int64_t M, int C, const float* probs, const int64_t* labels, const uint8_t* mask,
                                      float gamma, float weight, float* loss_sum, float* grad, float* ws,
                                      size_t ws_bytes, void* stream) {
-  SNV_CHECK_ARG(probs && labels && mask && loss_sum && grad, "null pointer");
+  SNV_CHECK_PTRS(probs, labels, mask, loss_sum, grad);
   SNV_CHECK_ARG(C >= 1 && C <= 4, "classes must be 1..4");
   if (M == 0) return 0;
   SNV_CHECK_ARG(ws && ws_bytes >= snvrag_focal_loss_det_ws_bytes(M),
@@ -207,7 +207,7 @@ extern "C" int snvrag_focal_loss_det(int64_t M, int C, const float* probs, const
 }
 
 static int sqnorm_impl(int64_t n, const float* x, float* acc, float* part, hipStream_t s) {
-  SNV_CHECK_ARG(x && acc && ((uintptr_t)x % 16) == 0, "null or misaligned pointer");
+  SNV_CHECK_ARG(x && acc && aligned(16, x), "null or misaligned pointer");
   if (n == 0) {
     SNV_HIP(hipMemsetAsync(acc, 0, sizeof(float), s));
     return 0;
@@ -233,7 +233,7 @@ extern "C" int snvrag_sqnorm_ws(int64_t n, const float* x, float* acc, float* ws
 
 extern "C" int snvrag_adam_step(int64_t n, float* p, const float* g, float* m, float* v, void* p_bf16,
                                 const float* sqnorm, const snvrag_adam_t* a, void* stream) {
-  SNV_CHECK_ARG(p && g && m && v && a, "null pointer");
+  SNV_CHECK_PTRS(p, g, m, v, a);
   SNV_CHECK_ARG(a->step >= 1, "step counts from 1");
   if (n == 0) return 0;
   hipStream_t s = as_stream(stream);
@@ -247,7 +247,7 @@ extern "C" int snvrag_adam_step(int64_t n, float* p, const float* g, float* m, f
 
 extern "C" int snvrag_confusion(int64_t M, int C, const float* probs, const int64_t* labels, const uint8_t* mask,
                                 const uint8_t* mask2, uint64_t* counts, void* stream) {
-  SNV_CHECK_ARG(probs && labels && mask && counts, "null pointer");
+  SNV_CHECK_PTRS(probs, labels, mask, counts);
   SNV_CHECK_ARG(C >= 1 && C <= 8, "classes must be 1..8");
   if (M == 0) return 0;
   hipLaunchKernelGGL(confusion_kernel, dim3(cdiv(M, 256)), dim3(256), 0, as_stream(stream), (long)M, C, probs,
@@ -1159,7 +1159,7 @@ extern "C" int snvrag_ln_fwd_train_act(int64_t M, int N, const void* x, const vo
                                        float p_out, uint64_t seed, float slope_x, float slope_r, void* stream) {
   SNV_CHECK_ARG(slope_x == 0.f || !r, "an input activation is for a norm without a residual");
   SNV_CHECK_ARG(slope_r == 0.f || r, "a residual activation needs a residual");
-  SNV_CHECK_ARG(x && g && b && y && stats, "null pointer");
+  SNV_CHECK_PTRS(x, g, b, y, stats);
   SNV_CHECK_ARG(N % 8 == 0 && N <= 64 * 8 * LN_MAXC, "N must be a multiple of 8, <= 2048");
   SNV_CHECK_ARG(!r || s_out, "a residual needs s_out");
   SNV_CHECK_ARG(p_r >= 0.f && p_r < 1.f && p_out >= 0.f && p_out < 1.f, "dropout probabilities must be in [0, 1)");
@@ -1206,7 +1206,7 @@ extern "C" int snvrag_ln_bwd_act(int64_t M, int N, const void* dy, const void* s
                                  void* ds, void* dres, const void* r_pre, float* dg, float* db, int accumulate,
                                  float p_r, float p_out, uint64_t seed, float slope_x, float slope_r, void* ws,
                                  size_t ws_bytes, void* stream) {
-  SNV_CHECK_ARG(dy && s && stats && g && ds && dg && db && ws, "null pointer");
+  SNV_CHECK_PTRS(dy, s, stats, g, ds, dg, db, ws);
   SNV_CHECK_ARG(N % 8 == 0 && N <= 64 * 8 * LN_MAXC, "N must be a multiple of 8, <= 2048");
   SNV_CHECK_ARG(ws_bytes >= snvrag_ln_bwd_ws_bytes(M, N), "workspace too small");
   SNV_CHECK_ARG(p_r >= 0.f && p_r < 1.f && p_out >= 0.f && p_out < 1.f, "dropout probabilities must be in [0, 1)");
@@ -1253,7 +1253,7 @@ extern "C" size_t snvrag_colsum_ws_bytes(int64_t M, int N) {
 
 extern "C" int snvrag_colsum_bf16(int64_t M, int N, const void* x, float* out, void* ws, size_t ws_bytes,
                                   void* stream) {
-  SNV_CHECK_ARG(x && out && ws, "null pointer");
+  SNV_CHECK_PTRS(x, out, ws);
   SNV_CHECK_ARG(N % 8 == 0 && N / 8 <= 256, "N must be a multiple of 8, <= 2048");
   SNV_CHECK_ARG(ws_bytes >= snvrag_colsum_ws_bytes(M, N), "workspace too small");
   hipStream_t st = as_stream(stream);
@@ -1273,7 +1273,7 @@ extern "C" int snvrag_colsum_bf16(int64_t M, int N, const void* x, float* out, v
 static int nbr_args(NbrArgs& a, int64_t nq, int k, int64_t L, int D, int n_sites, int64_t ld_codes, int V,
                     const int32_t* inv, const uint8_t* codes, const float* W, const float* pe, const float* Ar,
                     float p, uint64_t seed, int tok0, int sos, int eos, int pad) {
-  SNV_CHECK_ARG(inv && codes && W && pe && Ar, "null pointer");
+  SNV_CHECK_PTRS(inv, codes, W, pe, Ar);
   SNV_CHECK_ARG(D % 2 == 0 && D <= 2048 && V >= 1 && V * D <= 16384, "D even, V x D <= 16384");
   SNV_CHECK_ARG(n_sites + 2 <= L && ld_codes >= n_sites && k >= 1, "shape");
   SNV_CHECK_ARG(p >= 0.f && p < 1.f, "dropout probability must be in [0, 1)");
@@ -1291,7 +1291,7 @@ extern "C" int snvrag_nbr_mean_drop_fwd(int64_t nq, int k, int64_t L, int D, int
   NbrArgs a;
   if (int rc = nbr_args(a, nq, k, L, D, n_sites, ld_codes, V, inv, codes, W, pe, Ar, p, seed, tok0, sos, eos, pad))
     return rc;
-  SNV_CHECK_ARG(out, "null pointer");
+  SNV_CHECK_PTRS(out);
   if (nq == 0) return 0;
   const unsigned gy = (unsigned)std::min<int64_t>((nq + 3) / 4, 64);
   hipLaunchKernelGGL(nbr_mean_drop_fwd_kernel, dim3((unsigned)L, gy), dim3(256), 0, as_stream(stream), a, out);
@@ -1306,7 +1306,7 @@ extern "C" int snvrag_nbr_mean_drop_bwd(int64_t nq, int k, int64_t L, int D, int
   NbrArgs a;
   if (int rc = nbr_args(a, nq, k, L, D, n_sites, ld_codes, V, inv, codes, W, pe, Ar, p, seed, tok0, sos, eos, pad))
     return rc;
-  SNV_CHECK_ARG(dout && dW && dAr, "null pointer");
+  SNV_CHECK_PTRS(dout, dW, dAr);
   if (nq == 0) return 0;
   const int nthr = (int)std::min<long>(256, (D / 2 + 63) / 64 * 64);
   hipLaunchKernelGGL(nbr_mean_drop_bwd_kernel<false>, dim3((unsigned)L), dim3(nthr), (size_t)V * D * sizeof(float),
@@ -1327,7 +1327,7 @@ extern "C" int snvrag_nbr_mean_drop_bwd_det(int64_t nq, int k, int64_t L, int D,
   NbrArgs a;
   if (int rc = nbr_args(a, nq, k, L, D, n_sites, ld_codes, V, inv, codes, W, pe, Ar, p, seed, tok0, sos, eos, pad))
     return rc;
-  SNV_CHECK_ARG(dout && dW && dAr, "null pointer");
+  SNV_CHECK_PTRS(dout, dW, dAr);
   if (nq == 0) return 0;
   SNV_CHECK_ARG(ws && ws_bytes >= snvrag_nbr_mean_drop_bwd_det_ws_bytes(L, V, D),
                 "workspace smaller than snvrag_nbr_mean_drop_bwd_det_ws_bytes()");
@@ -1345,9 +1345,8 @@ extern "C" int snvrag_nbr_mean_drop_bwd_det(int64_t nq, int k, int64_t L, int D,
 extern "C" int snvrag_head2_fwd(int64_t M, int K, const void* x, const float* w, const float* b, float* out,
                                 void* stream) {
   if (M == 0) return 0;
-  SNV_CHECK_ARG(x && w && b && out, "null pointer");
-  SNV_CHECK_ARG(K % 8 == 0 && K > 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0,
-                "K % 8 == 0, 16-byte aligned x and w");
+  SNV_CHECK_PTRS(x, w, b, out);
+  SNV_CHECK_ARG(K % 8 == 0 && K > 0 && aligned(16, x, w), "K % 8 == 0, 16-byte aligned x and w");
   if (K == 1536)
     hipLaunchKernelGGL(head2_fwd_wave_kernel<3>, dim3((unsigned)cdiv(M, 64)), dim3(256), 0, as_stream(stream),
                        (long)M, (const bf16*)x, w, b, out);
@@ -1370,9 +1369,8 @@ extern "C" int snvrag_head2_bwd(int64_t M, int K, const float* g, const void* x,
     if (dw && !accumulate) SNV_HIP(hipMemsetAsync(dw, 0, (size_t)2 * K * sizeof(float), st));
     return 0;
   }
-  SNV_CHECK_ARG(g && x && w && ws, "null pointer");
-  SNV_CHECK_ARG(K % 8 == 0 && K > 0 && ((uintptr_t)x % 16) == 0 && (!dx || ((uintptr_t)dx % 16) == 0),
-                "K % 8 == 0, 16-byte aligned x / dx");
+  SNV_CHECK_PTRS(g, x, w, ws);
+  SNV_CHECK_ARG(K % 8 == 0 && K > 0 && aligned(16, x, dx), "K % 8 == 0, 16-byte aligned x / dx");
   SNV_CHECK_ARG(ws_bytes >= snvrag_head2_ws_bytes(M, K), "workspace too small");
   if (dx) {
     const long n8 = (long)M * (K / 8);
@@ -1400,9 +1398,9 @@ extern "C" size_t snvrag_tokgrad_ws_bytes(int64_t M, int V, int D) {
 
 extern "C" int snvrag_tokgrad(int64_t M, int V, int D, int padding_idx, const int64_t* tok, const float* g, float* dw,
                               void* ws, size_t ws_bytes, void* stream) {
-  SNV_CHECK_ARG(dw && ws, "null pointer");
+  SNV_CHECK_PTRS(dw, ws);
   SNV_CHECK_ARG(V >= 1 && V <= 16 && D % 2 == 0 && D > 0, "1 <= V <= 16 rows, even D");
-  SNV_CHECK_ARG(M == 0 || (tok && g && ((uintptr_t)g % 8) == 0), "tok / g (8-byte aligned)");
+  SNV_CHECK_ARG(M == 0 || (tok && g && aligned(8, g)), "tok / g (8-byte aligned)");
   SNV_CHECK_ARG(ws_bytes >= snvrag_tokgrad_ws_bytes(M, V, D), "workspace too small");
   hipStream_t st = as_stream(stream);
   if (M == 0) {

@@ -136,14 +136,14 @@ extern "C" int snvrag_vcf_format(int64_t n, int64_t S, const float* h1, const fl
                                  int64_t n_lines, const int32_t* rows, const int64_t* line_off,
                                  const int32_t* prefix_off, const uint8_t* prefix_blob, int64_t prefix_bytes,
                                  uint8_t* out, int64_t out_bytes, int32_t* bad_count, void* stream) {
-  SNV_CHECK_ARG(h1 && h2 && gt && rows && line_off && prefix_off && prefix_blob && out && bad_count, "null pointer");
+  SNV_CHECK_PTRS(h1, h2, gt, rows, line_off, prefix_off, prefix_blob, out, bad_count);
   SNV_CHECK_ARG(S >= 1 && S < (1LL << 31) / VCF_CELL, "S must be in [1, 2^31 / 40)");
   SNV_CHECK_ARG(n >= 1 && n < (1LL << 31), "n must be in [1, 2^31)");
   SNV_CHECK_ARG(n_lines >= 0, "n_lines must not be negative");
   SNV_CHECK_ARG(out_bytes >= 0 && out_bytes < (1LL << 31), "chunk bytes must be below 2^31");
   SNV_CHECK_ARG(prefix_bytes >= 0 && prefix_bytes < (1LL << 31), "prefix bytes must be below 2^31");
-  SNV_CHECK_ARG(((uintptr_t)out % 16) == 0 && ((uintptr_t)gt % 16) == 0, "out and gt must be 16-byte aligned");
-  SNV_CHECK_ARG(((uintptr_t)h1 % 4) == 0 && ((uintptr_t)h2 % 4) == 0, "h1 and h2 must be 4-byte aligned");
+  SNV_CHECK_ALIGN(16, "out and gt must be 16-byte aligned", out, gt);
+  SNV_CHECK_ALIGN(4, "h1 and h2 must be 4-byte aligned", h1, h2);
   // every line holds at least 40 S bytes of the chunk: more lines than that cannot be monotone offsets
   SNV_CHECK_ARG(n_lines <= out_bytes / (VCF_CELL * S), "n_lines lines of 40 S bytes exceed the chunk");
   if (n_lines == 0) return 0;

@@ -489,10 +489,10 @@ extern "C" size_t snvrag_vcf_line_index_ws_bytes(int64_t nbytes) {
 
 extern "C" int snvrag_vcf_line_index(const uint8_t* text, int64_t nbytes, int64_t max_lines, int64_t* line_off,
                                      int64_t* n_lines, void* ws, size_t ws_bytes, void* stream) {
-  SNV_CHECK_ARG(text && line_off && n_lines && ws, "null pointer");
+  SNV_CHECK_PTRS(text, line_off, n_lines, ws);
   SNV_CHECK_ARG(nbytes >= 1 && nbytes < (1LL << 31), "nbytes must be in [1, 2^31)");
   SNV_CHECK_ARG(max_lines >= 0, "max_lines must not be negative");
-  SNV_CHECK_ARG(((uintptr_t)text % 16) == 0 && ((uintptr_t)ws % 16) == 0 && ((uintptr_t)line_off % 8) == 0,
+  SNV_CHECK_ARG(aligned(16, text, ws) && aligned(8, line_off),
                 "text and ws must be 16-byte aligned, line_off 8-byte aligned");
   SNV_CHECK_ARG(ws_bytes >= snvrag_vcf_line_index_ws_bytes(nbytes), "workspace too small");
   const int nb = (int)((nbytes + LI_SPAN - 1) / LI_SPAN);
@@ -519,12 +519,12 @@ extern "C" size_t snvrag_vcf_parse_ws_bytes(int64_t n_lines, int64_t S) {
 extern "C" int snvrag_vcf_parse_gt(const uint8_t* text, int64_t nbytes, const int64_t* line_off, int64_t n_lines,
                                    int64_t S, int force_general, int32_t* pos, uint32_t* flags, uint8_t* codes,
                                    int64_t ld_codes, void* ws, size_t ws_bytes, void* stream) {
-  SNV_CHECK_ARG(text && line_off && pos && flags && codes && ws, "null pointer");
+  SNV_CHECK_PTRS(text, line_off, pos, flags, codes, ws);
   SNV_CHECK_ARG(nbytes >= 1 && nbytes < (1LL << 31), "nbytes must be in [1, 2^31)");
   SNV_CHECK_ARG(S >= 1 && S < (1LL << 29), "S must be in [1, 2^29)");
   SNV_CHECK_ARG(n_lines >= 0 && n_lines <= nbytes, "n_lines must be in [0, nbytes]");
   SNV_CHECK_ARG(ld_codes >= S && ld_codes % 4 == 0, "ld_codes must be a multiple of 4, at least S");
-  SNV_CHECK_ARG(((uintptr_t)text % 16) == 0 && ((uintptr_t)codes % 4) == 0 && ((uintptr_t)ws % 16) == 0,
+  SNV_CHECK_ARG(aligned(16, text, ws) && aligned(4, codes),
                 "text and ws must be 16-byte aligned, codes 4-byte aligned");
   SNV_CHECK_ARG(ws_bytes >= snvrag_vcf_parse_ws_bytes(n_lines, S), "workspace too small");
   if (n_lines == 0) return 0;
@@ -549,13 +549,13 @@ extern "C" int snvrag_vcf_parse_gt(const uint8_t* text, int64_t nbytes, const in
 extern "C" int snvrag_vcf_pack_rows(const uint8_t* codes, int64_t ld_codes, int64_t n_lines, int64_t S,
                                     int64_t site0, uint8_t* alt_bits, uint8_t* miss_bits, int64_t ld_bits,
                                     void* stream) {
-  SNV_CHECK_ARG(codes && alt_bits && miss_bits, "null pointer");
+  SNV_CHECK_PTRS(codes, alt_bits, miss_bits);
   SNV_CHECK_ARG(S >= 1 && S < (1LL << 29), "S must be in [1, 2^29)");
   SNV_CHECK_ARG(n_lines >= 0 && n_lines < (1LL << 40), "n_lines must be in [0, 2^40)");
   SNV_CHECK_ARG(ld_codes >= S && ld_codes % 4 == 0, "ld_codes must be a multiple of 4, at least S");
   SNV_CHECK_ARG(site0 >= 0 && site0 % 64 == 0, "site0 must be a non-negative multiple of 64");
   SNV_CHECK_ARG(ld_bits % 8 == 0 && ld_bits * 8 >= site0 + n_lines, "ld_bits must be a multiple of 8 that holds site0 + n_lines sites");
-  SNV_CHECK_ARG(((uintptr_t)codes % 4) == 0 && ((uintptr_t)alt_bits % 8) == 0 && ((uintptr_t)miss_bits % 8) == 0,
+  SNV_CHECK_ARG(aligned(4, codes) && aligned(8, alt_bits, miss_bits),
                 "codes must be 4-byte aligned, the bit rows 8-byte aligned");
   if (n_lines == 0) return 0;
   const int64_t stiles = (S + PK_SMP - 1) / PK_SMP, rtiles = (n_lines + PK_REC - 1) / PK_REC;
@@ -570,7 +570,7 @@ extern "C" int snvrag_vcf_pack_rows(const uint8_t* codes, int64_t ld_codes, int6
 extern "C" int snvrag_panel_gather_bits(const uint8_t* bits, int64_t N, int64_t ld_bits, int64_t n_src_sites,
                                         const int32_t* site_idx, int64_t n, int64_t n_sites_pad, int packed,
                                         uint8_t* out, void* stream) {
-  SNV_CHECK_ARG(bits && site_idx && out, "null pointer");
+  SNV_CHECK_PTRS(bits, site_idx, out);
   SNV_CHECK_ARG(N >= 0 && ld_bits >= 1, "N must not be negative, ld_bits at least 1");
   SNV_CHECK_ARG(n_src_sites >= 0 && n_src_sites <= 8 * ld_bits, "n_src_sites must be in [0, 8 ld_bits]");
   SNV_CHECK_ARG(n >= 0 && n <= n_sites_pad && n_sites_pad % 8 == 0 && n_sites_pad < (1LL << 31),
@@ -587,10 +587,10 @@ extern "C" int snvrag_panel_gather_bits(const uint8_t* bits, int64_t N, int64_t 
 
 extern "C" int snvrag_vcf_unpack_gt(const uint8_t* alt_bits, const uint8_t* miss_bits, int64_t ld_bits, int64_t S,
                                     int64_t n_sites, int8_t* gt, void* stream) {
-  SNV_CHECK_ARG(alt_bits && miss_bits && gt, "null pointer");
+  SNV_CHECK_PTRS(alt_bits, miss_bits, gt);
   SNV_CHECK_ARG(S >= 1 && S < (1LL << 29), "S must be in [1, 2^29)");
   SNV_CHECK_ARG(n_sites >= 0 && ld_bits * 8 >= n_sites, "ld_bits must hold n_sites sites");
-  SNV_CHECK_ARG(((uintptr_t)gt % 2) == 0, "gt must be 2-byte aligned");
+  SNV_CHECK_ALIGN(2, "gt must be 2-byte aligned", gt);
   if (n_sites == 0) return 0;
   const int64_t sblocks = (S + 255) / 256, rblocks = (n_sites + 7) / 8;
   SNV_CHECK_ARG(sblocks * rblocks < (1LL << 31), "blocks must be below 2^31");

@@ -142,10 +142,10 @@ _SIGS = {
     "snvrag_encoder_ws_bytes": ([C.c_int, i64, i64, C.c_int, C.c_int], sz),
     "snvrag_encoder_forward": ([C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.POINTER(LayerW), vp, vp, sz, vp],
                                C.c_int),
-    "snvrag_proj_pack_bytes": ([C.c_int, C.c_int], C.c_size_t),
+    "snvrag_proj_pack_bytes": ([C.c_int, C.c_int], sz),
     "snvrag_proj_pack": ([C.c_int, C.c_int, vp, vp, vp], C.c_int),
     "snvrag_proj_forward": ([i64, C.c_int, C.c_int, vp, vp, vp, vp, vp], C.c_int),
-    "snvrag_tail_pack_bytes": ([C.c_int], C.c_size_t),
+    "snvrag_tail_pack_bytes": ([C.c_int], sz),
     "snvrag_tail_pack": ([C.c_int, vp, vp, vp, vp, vp], C.c_int),
     "snvrag_tail_forward": ([i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, f32, vp], C.c_int),
     "snvrag_tail_qkv_forward": ([i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp], C.c_int),
@@ -189,7 +189,7 @@ _SIGS = {
     "snvrag_gemm256_pack_bytes": ([C.c_int, C.c_int], sz),
     "snvrag_gemm256_pack": ([C.c_int, C.c_int, vp, i64, vp, vp], C.c_int),
     "snvrag_gemm256_forward": ([i64, C.c_int, C.c_int, vp, i64, vp, vp, vp, i64, vp, i64, vp], C.c_int),
-    "snvrag_gemm256_ln_forward": ([i64, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, C.c_float, vp, i64, C.c_float,
+    "snvrag_gemm256_ln_forward": ([i64, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, f32, vp, i64, f32,
                                    vp, i64, vp, i64, vp], C.c_int),
     "snvrag_head2_fwd": ([i64, C.c_int, vp, vp, vp, vp, vp], C.c_int),
     "snvrag_head2_ws_bytes": ([i64, C.c_int], sz),
