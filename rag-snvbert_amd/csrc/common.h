@@ -42,7 +42,8 @@ struct Options {
   int64_t encoder_chunk;   // sequences per encoder chunk, 0 = auto
   int64_t gemm_tile128;    // 1: the 128-tile GEMM instead of the row-panel GEMM (tools/gemm_micro.py)
   int64_t gemm_nw;         // row-panel GEMM tile width (1, 2, 4, 6 x 64 columns), 0 = auto
-  int64_t tail_variant;    // block-tail diagnostic instantiation (tools/tail_micro.py), 0 = default
+  int64_t tail_variant;    // 4: tail_kernel with phase stamps into the snvrag_tail_stamps buffer (tools/tail_micro.py);
+                           // 0 and every other value: the default
   int64_t tail_desync;     // block-tail first-round stagger in cycles, -1 = auto
   int64_t sg_desync;       // stream-GEMM first-round stagger in cycles, -1 = auto
   int64_t mlp_desync;      // MLP kernel first-round stagger in cycles, -1 = auto
@@ -55,12 +56,12 @@ struct Options {
   int64_t g2_groups;       // wide-row GEMM token groups per workgroup (4 .. 8; 0: by M)
   int64_t g2_variant;      // wide-row GEMM diagnostics: 1 no LDS-DMA, 2 no MFMA (wrong results; timing only),
                            // 3 stamps into the snvrag_tail_stamps buffer
-  int64_t tail_persist;    // 1: the persistent block tail (tailp_kernel, A/B); 0 (default): tail_kernel
   int64_t tail_split;      // wide-row tail: split a last partial round of <= this many 128-row tiles into 32-row tiles (0: off)
   int64_t proj_wide;       // 1 (default): snvrag_proj_forward at D = 384 on the wide-row projection (tailw.hip,
                            // 0.62 vs 0.68 ms, bit-identical); 0: tail.hip PROJ mode
   int64_t tail_wide;       // block tail at D = 384 (PRE): 1 (default) the wide-row form (tailw.hip), 0 tail_kernel,
-                           // 2 the wide-row form with phase stamps into the snvrag_tail_stamps buffer
+                           // 2 the wide-row form with phase stamps into the snvrag_tail_stamps buffer; any other
+                           // value: the wide-row form
   int64_t tail_qkv;        // 1 (default): the encoder's wide-row tails also compute the NEXT layer's QKV projection
                            // (snvrag_tail_qkv_forward: no stand-alone QKV GEMM after layer 0); 0: one QKV launch per layer
   int64_t deterministic;   // 1: the Python wrappers route dW, the neighbour-mean backward and the focal loss to the
@@ -72,7 +73,7 @@ Options& options();
 unsigned long long* diag_stamps();
 
 // the wide-row block tail (tailw.hip), D = 384, PRE mode (out = LN2(FFN(LN1(x + att W_o^T))) in place);
-// pw != null: qkv_out[M, 3 D] = out W^T + pbias as well, W the snvrag_proj_pack stream pw (var 0 / 1 only)
+// pw != null: qkv_out[M, 3 D] = out W^T + pbias as well, W the snvrag_proj_pack stream pw; var 1: phase stamps
 int tailw_launch(int M, const void* att, const void* resid, void* out, const void* ws, const float* vec,
                  const float* b_o, const float* g1, const float* be1, float eps, int desync, int var,
                  const void* pw, const float* pbias, void* qkv_out, hipStream_t s);

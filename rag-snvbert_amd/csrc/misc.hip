@@ -102,11 +102,10 @@ const OptDesc kOpts[] = {
     {"tail_desync", &Options::tail_desync, -1},    {"sg_desync", &Options::sg_desync, -1},      {"mlp_desync", &Options::mlp_desync, -1},      {"g2_desync", &Options::g2_desync, -1},
     {"sg_waves4", &Options::sg_waves4, 0},         {"ln_bwd_nopf", &Options::ln_bwd_nopf, 0},
     {"attn_variant", &Options::attn_variant, 0},   {"dw_xcd", &Options::dw_xcd, 1},
-    {"ln_rows1", &Options::ln_rows1, 0},           {"tail_persist", &Options::tail_persist, 0},
-    {"tail_wide", &Options::tail_wide, 1},         {"proj_wide", &Options::proj_wide, 1},
-    {"g2_variant", &Options::g2_variant, 0},     {"g2_groups", &Options::g2_groups, 0},
-    {"tail_split", &Options::tail_split, 64},      {"deterministic", &Options::deterministic, 0},
-    {"tail_qkv", &Options::tail_qkv, 1},
+    {"ln_rows1", &Options::ln_rows1, 0},           {"tail_wide", &Options::tail_wide, 1},
+    {"proj_wide", &Options::proj_wide, 1},         {"g2_variant", &Options::g2_variant, 0},
+    {"g2_groups", &Options::g2_groups, 0},         {"tail_split", &Options::tail_split, 64},
+    {"deterministic", &Options::deterministic, 0}, {"tail_qkv", &Options::tail_qkv, 1},
 };
 Options make_options() {
   Options o{};

@@ -28,8 +28,6 @@
 namespace snvrag {
 
 constexpr int TL_NSLOT = 9;                 // ring slots (144 KiB)
-constexpr int TL_PF4 = 4;                   // A fragments read ahead: the template default and tail_variant 1
-constexpr int TL_PF_DEFAULT = 8;             // launch_tail's default (r3: 4: 1.634 ms, 8: 1.659 spilling; r5: 8 faster)
 constexpr int TL_ROWS = 128;
 constexpr int TL_VEC_LDS = 11 * 1024;       // b1 [4D] + g1, be1, b_o [D] (f32, D <= 384)
 
@@ -75,29 +73,33 @@ struct TailArgs {
   const float* vec;     // [b1 4D | b2' | c1 | g2 | be2]
   const float* b_o; const float* g1; const float* be1;
   float eps;
-  unsigned long long* stamps;   // VAR 2 (diagnostics): [workgroup][wave][TL_NSTAMP] s_memtime stamps
+  unsigned long long* stamps;   // STAMP (diagnostics): [workgroup][wave][TL_NSTAMP] s_memtime stamps
   int desync;                   // > 0: first-round phase step in cycles (stagger_wait, mfma32.h)
 };
 
-// diagnostic stamp points of VAR 2 (slot 0: s_memrealtime at entry, 1..: s_memtime)
+// diagnostic stamp points of STAMP (slot 0: s_memrealtime at entry, 1..: s_memtime)
 constexpr int TL_NSTAMP = 10;
 enum { TS_REAL0 = 0, TS_START, TS_PROLOGUE, TS_PROJ, TS_LN1, TS_FFN, TS_EPI, TS_END, TS_REAL1 };
 
-// VAR (diagnostics): 0 default; 1 = no weight DMA after the prologue (compute-side ceiling;
-// results are garbage); 2 = the default kernel plus per-wave s_memtime stamps at the phase
-// boundaries into p.stamps (a separate instantiation: no stamp executes in the real kernel);
-// 3 = residual added early (see RR_G).  TL_SGB: shape each slab's schedule as MFMA f / read f + PF pairs.
-// SNVRAG_TAIL_VARIANT (launch_tail): 1 = PF 8, 2 = VAR 1, 3 = no schedule groups, 4 = VAR 2
-// (stamps), 5 = VAR 3.
-// NC > 0: projection mode (snvrag_proj_forward): out[M, NC*D] = act W^T + b over NC output
-// chunks of D features (the QKV projection: NC = 3), the same stream / ring / read machinery.
-template <int D, bool PRE, int TL_PF = TL_PF4, int VAR = 0, bool TL_SGB = true, int NC = 0>
+// Modes: PRE = the whole tail (snvrag_tail_forward); !PRE = the FFN half from x1
+// (snvrag_tail_ffn_forward); NC > 0 = projection (snvrag_proj_forward): out[M, NC*D] =
+// act W^T + b over NC output chunks of D features (the QKV projection: NC = 3), on the same
+// stream / ring / read machinery.
+// STAMP (diagnostics, option tail_variant 4 with a snvrag_tail_stamps buffer): the kernel plus
+// per-wave s_memtime stamps at the phase boundaries into p.stamps; a separate instantiation,
+// so no stamp executes in the real kernel.
+// TL_PF, the A fragments read ahead of the MFMA that uses them: 8 in the tail modes (r3: 4
+// 1.634 ms, 8 1.659 ms spilling; r5: 8 faster), 4 in the projection.  The stamped kernel reads
+// 4 ahead, NOT the default's 8: its phase numbers in DESIGN.md were recorded at 4 and stay
+// comparable only with the same code.
+template <int D, bool PRE, int NC = 0, bool STAMP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void tail_kernel(TailArgs p) {
   using S = TailShape<D>;
   constexpr int NT = S::NT, KS = S::KS;
   constexpr bool PROJ = NC > 0;
-  static_assert(!(PROJ && PRE), "modes");
+  static_assert(!(PROJ && PRE) && !(PROJ && STAMP), "modes");
+  constexpr int TL_PF = (PROJ || STAMP) ? 4 : 8;
   constexpr int NSLAB = (PRE ? S::NPRE : 0) + S::NCH * S::SPC;      // slabs consumed by this launch
   constexpr int RING = TL_NSLOT * SLAB_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -109,11 +111,11 @@ void tail_kernel(TailArgs p) {
   const int ln = lane & 31, hh = lane >> 5;
   const long row = (long)blockIdx.x * TL_ROWS + wave * 32 + ln;
   const long rc = row < p.M ? row : (long)p.M - 1;
-  // (VAR 2) stamp: every lane writes the same value to the same slot through a vector store
+  // (STAMP) stamp: every lane writes the same value to the same slot through a vector store
   // (branch-free: an exec-masked store splits the unrolled stream into blocks and changes the
   // register allocation being measured)
   auto stamp = [&](int slot, bool real = false) {
-    if constexpr (VAR == 2) {
+    if constexpr (STAMP) {
       const unsigned long long t = real ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime();
       __builtin_nontemporal_store(t, p.stamps + ((long)blockIdx.x * 4 + wave) * TL_NSTAMP + slot);
     }
@@ -215,10 +217,6 @@ void tail_kernel(TailArgs p) {
   // the residual loads, have those NRR loads behind them in the vmcnt order)
   auto sync = [&](auto g_tag) {
     constexpr int g = decltype(g_tag)::value;
-    if constexpr (VAR == 1) {
-      __builtin_amdgcn_s_barrier();
-      return;
-    }
     if constexpr (PRE && g >= 0 && g <= TL_NSLOT - 2)
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (TL_NSLOT - 3) + NRR) : "memory");
     else
@@ -252,11 +250,9 @@ void tail_kernel(TailArgs p) {
       constexpr int qn = f + TL_PF;
       if constexpr (!STOP || qn < NF)
         a[f % TL_PF] = rdA(std::integral_constant<int, (qn >> 4)>{}, std::integral_constant<int, (qn & 15)>{});
-      if constexpr (TL_SGB) {
-        // pipeline shape for the scheduler: MFMA f, then the read PF fragments ahead
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
+      // pipeline shape for the scheduler: MFMA f, then the read PF fragments ahead
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
     }, std::make_integer_sequence<int, NF>{});
     rd_slot += (NF / 16) * SLAB_BYTES;
     rd_slot = rd_slot >= RING ? rd_slot - RING : rd_slot;
@@ -344,18 +340,8 @@ void tail_kernel(TailArgs p) {
     // xa[0..3], shifted down after each group (a straight-line 288-MFMA body makes hipcc
     // shuffle the accumulators between AGPRs)
     static_assert(KS % 4 == 0 && (4 * NT) % 16 == 0, "groups of 4 k-steps are whole slabs");
-    // VAR 3 (diagnostics): the residual x added into ao at the start of group 3 instead of in
-    // LN1's first pass (frees its registers before LN1, but waits for the residual burst earlier:
-    // measured slower, tools/tail_micro.py)
-    constexpr int RR_G = (VAR == 3 && KS / 4 > 3) ? 3 : -1;
     unroll([&](auto gc) {
       constexpr int g = decltype(gc)::value;
-      if constexpr (g == RR_G) {
-#pragma unroll
-        for (int T = 0; T < NT; ++T)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) ao[T][i] += bf_at(rr[2 * T + (i >> 3)], i & 7);
-      }
       run(std::integral_constant<int, 4 * NT>{}, std::integral_constant<int, g * (NT / 4)>{}, [&](auto fc, const u32x4& A) {
         constexpr int f = decltype(fc)::value;
         ao[f % NT] = mfma32(A, xa[4 * g + f / NT], ao[f % NT]);
@@ -369,11 +355,8 @@ void tail_kernel(TailArgs p) {
     for (int T = 0; T < NT; ++T)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        float v = ao[T][i];
-        if constexpr (RR_G < 0) {
-          v += bf_at(rr[2 * T + (i >> 3)], i & 7);
-          ao[T][i] = v;
-        }
+        const float v = ao[T][i] + bf_at(rr[2 * T + (i >> 3)], i & 7);
+        ao[T][i] = v;
         sum += v;
         sq = fmaf(v, v, sq);
       }
@@ -545,473 +528,10 @@ void tail_kernel(TailArgs p) {
                   pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
     }
   }
-  if constexpr (VAR == 2) {
+  if constexpr (STAMP) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the row stores have left
     stamp(TS_END);
     stamp(TS_REAL1, true);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// PERSISTENT block tail (PRE mode, the engine's path): one workgroup per CU loops over 128-row
-// tiles (tile = blockIdx.x, + gridDim.x, ...) with ONE continuous LDS-DMA ring across them.  Per
-// tile the ring streams, in consumption order,
-//   A  the tile's attention rows  (KS / 4 slabs; wave w's pieces = its 32 rows, 4 k-steps each)
-//   Wo the W_o' fragments         (NPRE slabs)
-//   R  the tile's residual rows x (KS / 4 slabs; features 32 T + 16 hh + 8 h2 per piece)
-//   W1 / W2' chunk blocks         (NCH x SPC slabs, the per-workgroup rotation of tail_kernel)
-// so the activations of tile t + 1 arrive by DMA while tile t finishes its FFN, instead of every
-// workgroup waiting on a 192 KB HBM burst of its own before its first MFMA (tail_kernel: the
-// prologue was 12 % of a wave's cycles, the ring drain + epilogue table loads another ~4 %).  The
-// epilogue's vector tables stay in LDS for the whole launch (8-slot ring: 128 KiB + 11 D floats).
-// The arithmetic is tail_kernel's, in the same order: outputs are bit-identical to it.
-// LDS-DMA is issued by inline asm (dma_x4): the compiler sees no LDS stores, so its own LDS reads
-// (vector tables, A / R pieces) get no waits on the weight stream; the ordering is this kernel's
-// counted vmcnt + barrier.  The 2 NT epilogue stores of a tile are buffer stores (rows >= M fall
-// outside the resource), so every tile issues the same vector-memory count and the first syncs of
-// the next tile wait with that count added.
-constexpr int TP_NSLOT = 8;
-
-// STAMP (diagnostics, a separate instantiation): s_memtime at the phase boundaries of each tile,
-// the last tile's kept in SGPRs and written out at exit: [workgroup][wave][TP_NSTAMP] u32
-constexpr int TP_NSTAMP = 8;
-template <int D, bool STAMP = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void tailp_kernel(TailArgs p) {
-  using S = TailShape<D>;
-  constexpr int NT = S::NT, KS = S::KS;
-  constexpr int NA = KS / 4;                          // A (and R) slabs per tile
-  // per tile, NA groups of GS slabs: [A_g, W_o' (NT / 4 slabs: k-steps 4 g .. 4 g + 3), R_g],
-  // then the FFN: the activation slabs are consumed beside the out-projection's MFMAs, never
-  // several in a row (a run of MFMA-free slabs would use up the ring's lookahead)
-  constexpr int WPG = NT / 4;                         // W_o' slabs per group
-  constexpr int GS = WPG + 2;
-  constexpr int Q_FFN = NA * GS;
-  static_assert(S::NPRE == NA * WPG, "W_o' groups");
-  constexpr int NQ = Q_FFN + S::NCH * S::SPC;         // slabs per tile
-  constexpr int AHEAD = TP_NSLOT - 2;                 // sync(g) issues slab g + AHEAD
-  constexpr int RING = TP_NSLOT * SLAB_BYTES;
-  constexpr int VM = 4 * (TP_NSLOT - 3);              // vmcnt at a sync: the younger slabs in flight
-  constexpr int NST = 2 * NT;                         // epilogue stores per lane and tile
-  constexpr int H = S::FW1 / 16;                      // slabs per W1 / W2' block
-  constexpr int NB2 = 2 * S::NCH;                     // FFN blocks per tile
-  static_assert(VM + NST <= 63, "vmcnt range");
-  static_assert(KS % 4 == 0 && H == S::FW2 / 16, "whole A / R slabs, equal W1 / W2' blocks");
-  // FFN block layout of a tile: phase1(0), phase1(1), phase2, phase1(2), phase2, then a runtime
-  // loop of 4 blocks per iteration over chunks 3 .. NCH - 4, its last iteration peeled (compile-time
-  // issue targets there: the last block W2'(N-1) breaks the loop's block pattern), then
-  // phase1(NCH - 1), phase2, phase2
-  // loop iterations (chunk pairs 3 .. NCH - 2): the runtime ones are those whose issue targets
-  // (AHEAD slabs past their last part) stay inside plain blocks; the rest are unrolled
-  constexpr int NIT = (S::NCH - 4) / 2;
-  constexpr int LIT_MAX = ((NB2 - 1) * H - 1 - AHEAD - 9 * H);
-  constexpr int LOOP_IT = LIT_MAX < 0 ? 0 : (LIT_MAX / (4 * H) + 1 < NIT ? LIT_MAX / (4 * H) + 1 : NIT);
-  static_assert(S::NCH % 2 == 0 && S::NCH >= 6, "chunk pairs");
-  constexpr int Q_LOOP = Q_FFN + 5 * H;               // first slab of the loop
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* ring = smem;
-  float* sv = reinterpret_cast<float*>(smem + RING);  // [b1 4D | b2' | c1 | g2 | be2 | g1 | be1 | b_o]
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int hh = lane >> 5;
-  const int M = p.M;
-  const int ntiles = (M + TL_ROWS - 1) / TL_ROWS;
-  const int G = gridDim.x;
-
-  for (int i = tid; i < 8 * D; i += 256) sv[i] = p.vec[i];
-  for (int i = tid; i < D; i += 256) { sv[8 * D + i] = p.g1[i]; sv[9 * D + i] = p.be1[i]; sv[10 * D + i] = p.b_o[i]; }
-  // first-tile stagger (tail_kernel's desync), only for the workgroups with one tile fewer: their
-  // slack absorbs it
-  if (p.desync > 0 && ntiles % G != 0 && (int)blockIdx.x >= ntiles % G && ntiles >= 8 * G) stagger_wait(p.desync);
-
-  // ---- issue side.  Every issue target is a compile-time tile-relative slab index (the loop's
-  // are compile-time offsets from the iteration's runtime block base), so an issue is a few scalar
-  // adds: the weight stream offset of an FFN block is (NPRE + H m) slabs with m = 2 rot + s + d(s)
-  // mod 2 NCH (tail_kernel's rotated order), the activation pieces through a resource starting at
-  // the tile's rows (rows >= M, and tiles >= ntiles, read as zeros).
-  const int rot2 = 2 * (int)(blockIdx.x % S::NCH);
-  const i32x4 wrs = dma_rsrc(p.ws, (long)S::NSLAB * SLAB_BYTES);
-  const uint32_t ring_lds = lds_addr(ring) + wave * 4 * FRAG_BYTES;
-  const int wave_off = wave * 4 * FRAG_BYTES;
-  int is_slot = 0;                                    // ring slot (byte offset) of the next issue
-  long tb = (long)blockIdx.x * TL_ROWS * D * 2;       // byte offset of the current tile's rows
-  constexpr int TB_STEP = TL_ROWS * D * 2;
-  // wave-uniform values made opaque at each use: otherwise hipcc precomputes every issue's
-  // offset (each a loop-invariant scalar) before the tile loop and spills ~250 SGPRs
-  auto opq = [](auto v) { asm volatile("" : "+s"(v)); return v; };
-  // A / R piece j of this wave: 8 of its rows x the slab's 128 B of each (4 k-steps / 2 residual
-  // tiles), i.e. 8 whole 128-B lines per DMA instruction; LDS image [32 rows][128 B] with the
-  // 16-B chunks XOR-swizzled by row & 7 (conflict-free fragment reads): lane l fills row
-  // 8 j + l / 8, slot l % 8, so it loads chunk (l % 8) ^ (row % 8).  From a fresh lane id.
-  auto voff_act = [&](int j) {
-    const int l = lane_id();
-    return (opq(wave) * 32 + 8 * j + (l >> 3)) * (D * 2) + 16 * ((l & 7) ^ ((l >> 3) & 7));
-  };
-  auto put = [&](const i32x4& rs, int soff, bool act) {
-    const int lds = opq(ring_lds) + is_slot;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      dma_x4(rs, lds + j * FRAG_BYTES, act ? voff_act(j) : lane_id() * 16, act ? soff : soff + j * FRAG_BYTES);
-    is_slot = is_slot + SLAB_BYTES == RING ? 0 : is_slot + SLAB_BYTES;
-  };
-  auto ffn_off = [&](int m) {                         // m in [0, 2 NB2)
-    m = m >= NB2 ? m - NB2 : m;
-    return (S::NPRE * SLAB_BYTES) + m * (H * SLAB_BYTES);
-  };
-  // target QG: tile-relative slab (>= NQ: the next tile's); compile-time
-  auto issue_ct = [&](auto q_tag) {
-    constexpr int QG = decltype(q_tag)::value;
-    constexpr bool NEXT = QG >= NQ;
-    constexpr int q = NEXT ? QG - NQ : QG;
-    constexpr int gq = q / GS, rq = q % GS;
-    if constexpr (q < Q_FFN && (rq == 0 || rq == GS - 1)) {
-      // A_g / R_g.  A resource over the tile's rows to the end of the array: the buffer range
-      // check covers voffset, not soffset, so the tile offset goes into the base (rows >= M read
-      // as zeros)
-      const long tbl = NEXT ? opq(tb) + (long)G * TB_STEP : opq(tb);
-      const long left = (long)M * D * 2 - tbl;
-      const char* base = reinterpret_cast<const char*>(rq == 0 ? p.act : p.resid);
-      put(dma_rsrc(base + (left > 0 ? tbl : 0), left > 0 ? left : 0), 128 * gq, true);
-    } else if constexpr (q < Q_FFN) {
-      put(wrs, (gq * WPG + rq - 1) * SLAB_BYTES + opq(wave_off), false);
-    } else {
-      constexpr int qq = q - Q_FFN, sb = qq / H, jb = qq % H;
-      constexpr int d = (sb == 0 || sb == NB2 - 1) ? 0 : (sb & 1) ? 1 : -1;
-      put(wrs, ffn_off(opq(rot2) + sb + d) + jb * SLAB_BYTES + opq(wave_off), false);
-    }
-  };
-  // loop target: slab Q_LOOP + AHEAD + 4 H it + C; mloop = rot2 + 4 it (runtime)
-  auto issue_loop = [&](auto c_tag, int mloop) {
-    constexpr int C = decltype(c_tag)::value;
-    constexpr int qq = Q_LOOP + AHEAD - Q_FFN + C, sb = qq / H, jb = qq % H;   // block of iteration 0
-    constexpr int d = (sb & 1) ? 1 : -1;
-    static_assert(sb > 0 && sb + 4 * (LOOP_IT - 1) < NB2 - 1, "loop targets are plain blocks");
-    put(wrs, ffn_off(mloop + sb + d) + jb * SLAB_BYTES + opq(wave_off), false);
-  };
-  // the vector tables landed (plain loads), then the first AHEAD slabs
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  unroll([&](auto gc) { issue_ct(gc); }, std::make_integer_sequence<int, AHEAD>{});
-
-  // sync before reading slab g: it has landed (this wave's pieces: vmcnt; the others': barrier)
-  auto wait_bar = [&](auto vm_tag) {
-    constexpr int V = decltype(vm_tag)::value;
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(V) : "memory");
-    __builtin_amdgcn_s_barrier();
-  };
-  using VMc = std::integral_constant<int, VM>;
-  using VMs = std::integral_constant<int, VM + NST>;
-  // the syncs of a tile's slabs 1 .. AHEAD: issued before the previous tile's epilogue stores (the
-  // first tile issues as many no-op stores at the same point), so those are among the younger
-  auto vm_of = [](auto g_tag) {
-    constexpr int g = decltype(g_tag)::value;
-    return std::conditional_t<(g >= 1 && g <= AHEAD), VMs, VMc>{};
-  };
-  // sync of compile-time slab G (then slab G + AHEAD goes into the slot of slab G - 2)
-  auto sync_ct = [&](auto g_tag, auto vm_tag) {
-    wait_bar(vm_tag);
-    issue_ct(std::integral_constant<int, decltype(g_tag)::value + AHEAD>{});
-  };
-
-  int rd_slot = 0;
-  auto rdA = [&](auto j_tag, auto fi_tag) -> u32x4 {
-    constexpr int j = decltype(j_tag)::value, fi = decltype(fi_tag)::value;
-    int so = rd_slot + j * SLAB_BYTES;
-    so = so >= RING ? so - RING : so;
-    return *reinterpret_cast<const u32x4*>(ring + so + lane * 16 + fi * FRAG_BYTES);
-  };
-  // B fragment j of this wave's rows in the current A / R slab (features 64 slab + 32 (j / 2) +
-  // 16 hh + 8 (j % 2) .. + 7 of row ln: 16-B chunk 4 (j / 2) + 2 hh + j % 2 of the row's 128 B)
-  auto rdOwn = [&](int j) -> u32x4 {
-    const int l = lane_id(), ln = l & 31;
-    const int c = 4 * (j >> 1) + 2 * (l >> 5) + (j & 1);
-    return *reinterpret_cast<const u32x4*>(ring + rd_slot + opq(wave_off) + ln * 128 + 16 * (c ^ (ln & 7)));
-  };
-  auto advance = [&](int n) {
-    rd_slot += n * SLAB_BYTES;
-    rd_slot = rd_slot >= RING ? rd_slot - RING : rd_slot;
-  };
-
-  constexpr int PF = TL_PF4;
-  u32x4 a[PF];
-  // consume a part of NF fragments (whole slabs) starting at tile slab G0 (compile-time), or, with
-  // G0 < 0, the loop part at block offset P of the iteration whose issue base is mloop
-  auto run = [&](auto nf_tag, auto g0_tag, auto p_tag, int mloop, auto&& mma, auto stop_tag) {
-    constexpr int NF = decltype(nf_tag)::value;
-    constexpr int G0 = decltype(g0_tag)::value;
-    constexpr int P = decltype(p_tag)::value;
-    constexpr bool STOP = decltype(stop_tag)::value;
-    static_assert(NF % 16 == 0, "parts are whole slabs");
-    unroll([&](auto fc) {
-      constexpr int f = decltype(fc)::value;
-      const u32x4 cur = a[f % PF];
-      if constexpr ((f & 15) == 16 - PF) {
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (G0 >= 0) {
-          wait_bar(vm_of(std::integral_constant<int, G0 + (f >> 4) + 1>{}));
-          issue_ct(std::integral_constant<int, G0 + (f >> 4) + 1 + AHEAD>{});
-        } else {
-          wait_bar(VMc{});
-          issue_loop(std::integral_constant<int, P + (f >> 4) + 1>{}, mloop);
-        }
-      }
-      mma(fc, cur);
-      constexpr int qn = f + PF;
-      if constexpr (!STOP || qn < NF)
-        a[f % PF] = rdA(std::integral_constant<int, (qn >> 4)>{}, std::integral_constant<int, (qn & 15)>{});
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }, std::make_integer_sequence<int, NF>{});
-    advance(NF / 16);
-  };
-  auto prime = [&]() {
-    unroll([&](auto ic) { a[decltype(ic)::value] = rdA(std::integral_constant<int, 0>{}, ic); },
-              std::make_integer_sequence<int, PF>{});
-  };
-  using I0 = std::integral_constant<int, 0>;
-
-  // table t, tile T: this lane's 16 floats (features 32 T + 16 hh + i)
-  auto tab = [&](int t, int T, float (&v)[16]) {
-    ld16(opq(lds_byte_addr(sv)) + 4 * (t * D + 32 * T) + 64 * (lane_id() >> 5), v);
-  };
-  enum { TB_B2 = 4, TB_C1 = 5, TB_G2 = 6, TB_BE2 = 7, TB_G1 = 8, TB_BE1 = 9, TB_BO = 10 };
-  const long out_bytes = (long)M * D * 2;
-  const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)p.out, (short)0, (int)(out_bytes < 0x7fffffffL ? out_bytes : 0x7fffffffL), 0x00020000);
-
-  uint32_t st[TP_NSTAMP] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll 1
-  for (int t = blockIdx.x; t < ntiles; t += G, tb += (long)G * TB_STEP) {
-    auto mark = [&](int i) {
-      if constexpr (STAMP) st[i] = (uint32_t)__builtin_amdgcn_s_memtime();
-    };
-    mark(0);
-    // ---- first tile: slab 0 and the stand-ins for the previous tile's epilogue stores
-    if (t == (int)blockIdx.x) {
-      sync_ct(std::integral_constant<int, 0>{}, VMc{});
-      const __amdgpu_buffer_rsrc_t nrs = __builtin_amdgcn_make_buffer_rsrc(p.out, (short)0, 0, 0x00020000);
-#pragma unroll
-      for (int i = 0; i < NST; ++i) __builtin_amdgcn_raw_buffer_store_b128(a[0], nrs, 0, 0, 0);   // (dropped)
-    }
-    mark(1);
-    // ---- ao = b_o + att W_o'^T, group by group: A_g (the attention rows' k-steps 4 g .. 4 g + 3 as
-    // B fragments), the group's W_o' slabs, then R_g (residual tiles 2 g, 2 g + 1) into rr
-    f32x16 ao[NT];
-#pragma unroll
-    for (int T = 0; T < NT; ++T) {
-      float bo[16];
-      tab(TB_BO, T, bo);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) ao[T][i] = bo[i];
-    }
-    u32x4 rr[2 * NT];
-    unroll([&](auto gc) {
-      constexpr int g = decltype(gc)::value;
-      constexpr int QA = g * GS;
-      if constexpr (g > 0) sync_ct(std::integral_constant<int, QA>{}, vm_of(std::integral_constant<int, QA>{}));
-      u32x4 xa[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) xa[j] = rdOwn(j);
-      advance(1);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // in registers before the slot recycles
-      sync_ct(std::integral_constant<int, QA + 1>{}, vm_of(std::integral_constant<int, QA + 1>{}));
-      prime();
-      run(std::integral_constant<int, 4 * NT>{}, std::integral_constant<int, QA + 1>{}, I0{}, 0,
-          [&](auto fc, const u32x4& A) {
-            constexpr int f = decltype(fc)::value;
-            ao[f % NT] = mfma32(A, xa[f / NT], ao[f % NT]);
-          }, std::true_type{});
-#pragma unroll
-      for (int j = 0; j < 4; ++j) rr[4 * g + j] = rdOwn(j);
-      advance(1);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }, std::make_integer_sequence<int, NA>{});
-    mark(2);
-    sync_ct(std::integral_constant<int, Q_FFN>{}, vm_of(std::integral_constant<int, Q_FFN>{}));   // the first FFN slab
-    mark(3);
-    // ---- x1 = LN1(ao + x) -> xr
-    u32x4 xr[KS];
-    {
-      float sum = 0.f, sq = 0.f;
-#pragma unroll
-      for (int T = 0; T < NT; ++T)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float v = ao[T][i] + bf_at(rr[2 * T + (i >> 3)], i & 7);
-          ao[T][i] = v;
-          sum += v;
-          sq = fmaf(v, v, sq);
-        }
-#pragma unroll
-      for (int T = 0; T < NT; ++T) asm volatile("" : "+a"(ao[T]));
-      asm volatile("" ::: "memory");
-      sum = xsum32(sum);
-      sq = xsum32(sq);
-      const float mean = sum * (1.0f / D);
-      const float rstd = 1.0f / sqrtf(fmaxf(sq * (1.0f / D) - mean * mean, 0.f) + p.eps);
-#pragma unroll
-      for (int T = 0; T < NT; ++T) {
-        float y[16], g1v[16], be1v[16];
-        tab(TB_G1, T, g1v);
-        tab(TB_BE1, T, be1v);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) y[i] = (ao[T][i] - mean) * rstd * g1v[i] + be1v[i];
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2)
-          xr[2 * T + h2] = u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                                 pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])};
-      }
-    }
-    prime();
-#pragma unroll
-    for (int k = 0; k < KS; ++k) asm volatile("" : "+v"(xr[k]));
-
-    mark(4);
-    // ---- FFN (tail_kernel's software pipeline)
-    f32x16 acc[NT];
-    float st1 = 0.f, st2 = 0.f;
-    f32x16 h0[2], h1[2];
-    u32x4 hf[4];
-    auto epi_pair = [&](const f32x16 (&hc)[2], int m) {
-      const int tt = m >> 3, i = 2 * (m & 7);
-      float x0 = hc[tt][i], x1 = hc[tt][i + 1];
-      x0 = lrelu(x0);
-      x1 = lrelu(x1);
-      st1 += x0 + x1;
-      st2 = fmaf(x0, x0, fmaf(x1, x1, st2));
-      hf[2 * tt + (i >> 3)][(i & 7) >> 1] = pack2(x0, x1);
-    };
-    // G0: the part's first tile slab (compile-time) or < 0 for a loop part at block offset P
-    auto phase1 = [&](int k, f32x16 (&hn)[2], const f32x16 (&hc)[2], auto epi_tag, auto g0_tag, auto p_tag,
-                      int mloop) {
-      constexpr bool EPI = decltype(epi_tag)::value;
-      int c = k + (int)((unsigned)opq(rot2) >> 1);
-      c = c >= S::NCH ? c - S::NCH : c;
-      const uint32_t b1 = opq(lds_byte_addr(sv)) + 16 * (lane_id() >> 5) + 256 * c;
-      u32x4 bv[8];
-      asm volatile(
-          "ds_read_b128 %0, %8 offset:0\n ds_read_b128 %1, %8 offset:32\n ds_read_b128 %2, %8 offset:64\n"
-          " ds_read_b128 %3, %8 offset:96\n ds_read_b128 %4, %8 offset:128\n ds_read_b128 %5, %8 offset:160\n"
-          " ds_read_b128 %6, %8 offset:192\n ds_read_b128 %7, %8 offset:224\n s_waitcnt lgkmcnt(0)"
-          : "=&v"(bv[0]), "=&v"(bv[1]), "=&v"(bv[2]), "=&v"(bv[3]), "=&v"(bv[4]), "=&v"(bv[5]), "=&v"(bv[6]),
-            "=&v"(bv[7])
-          : "v"(b1));
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) hn[tt][4 * r + e] = __uint_as_float(bv[4 * tt + r][e]);
-      run(std::integral_constant<int, S::FW1>{}, g0_tag, p_tag, mloop, [&](auto fc, const u32x4& A) {
-        constexpr int f = decltype(fc)::value;
-        hn[f & 1] = mfma32(A, xr[f >> 1], hn[f & 1]);
-        constexpr int SP = S::FW1 / 16;
-        if constexpr (EPI && f % SP == 0) epi_pair(hc, f / SP);
-      }, std::false_type{});
-    };
-    auto phase2 = [&](auto first_tag, auto stop_tag, auto g0_tag, auto p_tag, int mloop) {
-      constexpr bool FIRST = decltype(first_tag)::value;
-      run(std::integral_constant<int, S::FW2>{}, g0_tag, p_tag, mloop, [&](auto fc, const u32x4& A) {
-        constexpr int f = decltype(fc)::value;
-        if constexpr (FIRST && f < NT) acc[f] = mfma32(A, hf[0], f32x16{});
-        else acc[f % NT] = mfma32(A, hf[f / NT], acc[f % NT]);
-      }, stop_tag);
-    };
-    using F_ = std::false_type;
-    using T_ = std::true_type;
-    auto at = [](auto blk) { return std::integral_constant<int, Q_FFN + decltype(blk)::value * H>{}; };
-    using B0 = std::integral_constant<int, 0>;
-    using B1 = std::integral_constant<int, 1>;
-    using B2 = std::integral_constant<int, 2>;
-    using B3 = std::integral_constant<int, 3>;
-    using B4 = std::integral_constant<int, 4>;
-    phase1(0, h0, h1, F_{}, at(B0{}), I0{}, 0);
-    phase1(1, h1, h0, T_{}, at(B1{}), I0{}, 0);
-    phase2(T_{}, F_{}, at(B2{}), I0{}, 0);
-    phase1(2, h0, h1, T_{}, at(B3{}), I0{}, 0);
-    phase2(F_{}, F_{}, at(B4{}), I0{}, 0);
-    using LP = std::integral_constant<int, -1>;
-    int mloop = rot2;
-#pragma unroll 1
-    for (int it = 0; it < LOOP_IT; ++it, mloop += 4) {
-      const int k = 3 + 2 * it;
-      phase1(k, h1, h0, T_{}, LP{}, std::integral_constant<int, 0>{}, mloop);
-      phase2(F_{}, F_{}, LP{}, std::integral_constant<int, H>{}, mloop);
-      phase1(k + 1, h0, h1, T_{}, LP{}, std::integral_constant<int, 2 * H>{}, mloop);
-      phase2(F_{}, F_{}, LP{}, std::integral_constant<int, 3 * H>{}, mloop);
-    }
-    // the remaining iterations, unrolled: compile-time issue targets (they reach W2'(N-1) and
-    // the next tile)
-    unroll([&](auto ic) {
-      constexpr int it = LOOP_IT + decltype(ic)::value;
-      constexpr int kb = 5 + 4 * it;                      // its first block
-      constexpr int k = 3 + 2 * it;
-      phase1(k, h1, h0, T_{}, at(std::integral_constant<int, kb>{}), I0{}, 0);
-      phase2(F_{}, F_{}, at(std::integral_constant<int, kb + 1>{}), I0{}, 0);
-      phase1(k + 1, h0, h1, T_{}, at(std::integral_constant<int, kb + 2>{}), I0{}, 0);
-      phase2(F_{}, F_{}, at(std::integral_constant<int, kb + 3>{}), I0{}, 0);
-    }, std::make_integer_sequence<int, NIT - LOOP_IT>{});
-    static_assert(5 + 4 * NIT == NB2 - 3, "block schedule");
-    phase1(S::NCH - 1, h1, h0, T_{}, at(std::integral_constant<int, NB2 - 3>{}), I0{}, 0);
-    phase2(F_{}, F_{}, at(std::integral_constant<int, NB2 - 2>{}), I0{}, 0);
-#pragma unroll
-    for (int m = 0; m < 16; ++m) epi_pair(h1, m);
-    // the last part syncs the next tile's slab 0 and stops reading there
-    phase2(F_{}, T_{}, at(std::integral_constant<int, NB2 - 1>{}), I0{}, 0);
-
-    mark(5);
-    // ---- epilogue: out = LN2(x1 + lrelu(rstd_f acc - rstd_f mean_f c1 + b2'))
-    st1 = xsum32(st1);
-    st2 = xsum32(st2);
-    const float hm = st1 * (1.0f / (4 * D));
-    const float hr = 1.0f / sqrtf(fmaxf(st2 * (1.0f / (4 * D)) - hm * hm, 0.f) + p.eps);
-    float sum = 0.f, sq = 0.f;
-#pragma unroll
-    for (int T = 0; T < NT; ++T) {
-      float c1v[16], b2v[16];
-      tab(TB_C1, T, c1v);
-      tab(TB_B2, T, b2v);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        float u = hr * fmaf(-hm, c1v[i], acc[T][i]) + b2v[i];
-        u = lrelu(u);
-        const float v = u + bf_at(xr[2 * T + (i >> 3)], i & 7);
-        acc[T][i] = v;
-        sum += v;
-        sq = fmaf(v, v, sq);
-      }
-    }
-#pragma unroll
-    for (int T = 0; T < NT; ++T) asm volatile("" : "+a"(acc[T]));
-    asm volatile("" ::: "memory");
-    sum = xsum32(sum);
-    sq = xsum32(sq);
-    const float mean = sum * (1.0f / D);
-    const float rstd = 1.0f / sqrtf(fmaxf(sq * (1.0f / D) - mean * mean, 0.f) + p.eps);
-    const float nmr = -mean * rstd;
-    const int row_off = (int)(((long)t * TL_ROWS + wave * 32 + (lane_id() & 31)) * D + 16 * (lane_id() >> 5)) * 2;
-#pragma unroll
-    for (int T = 0; T < NT; ++T) {
-      float y[16], g2v[16], be2v[16];
-      tab(TB_G2, T, g2v);
-      tab(TB_BE2, T, be2v);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) y[i] = fmaf(fmaf(acc[T][i], rstd, nmr), g2v[i], be2v[i]);
-#pragma unroll
-      for (int h2 = 0; h2 < 2; ++h2)
-        __builtin_amdgcn_raw_buffer_store_b128(
-            u32x4{pack2(y[8 * h2], y[8 * h2 + 1]), pack2(y[8 * h2 + 2], y[8 * h2 + 3]),
-                  pack2(y[8 * h2 + 4], y[8 * h2 + 5]), pack2(y[8 * h2 + 6], y[8 * h2 + 7])},
-            ors, row_off + 64 * T + 16 * h2, 0, 0);
-    }
-    mark(6);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the ring overrun has landed before exit
-  if constexpr (STAMP) {
-    st[7] = (uint32_t)__builtin_amdgcn_s_memtime();
-    uint32_t* o = reinterpret_cast<uint32_t*>(p.stamps) + ((long)blockIdx.x * 4 + wave) * TP_NSTAMP;
-#pragma unroll
-    for (int i = 0; i < TP_NSTAMP; ++i) o[i] = st[i];
   }
 }
 
@@ -1062,7 +582,7 @@ __global__ void proj_pack_kernel(int D, long n_pieces, const bf16* __restrict__ 
 
 template <int D, int NC>
 static int launch_proj(const TailArgs& a, hipStream_t s) {
-  auto kern = tail_kernel<D, false, TL_PF4, 0, true, NC>;
+  auto kern = tail_kernel<D, false, NC>;
   constexpr size_t lds = (size_t)TL_NSLOT * SLAB_BYTES + NC * D * 4;
   static_assert(NC * D * 4 <= TL_VEC_LDS && lds <= 160 * 1024, "LDS budget");
   return SNV_LAUNCH_LDS(kern, dim3((unsigned)cdiv(a.M, TL_ROWS)), dim3(256), lds, s, a);
@@ -1070,21 +590,6 @@ static int launch_proj(const TailArgs& a, hipStream_t s) {
 
 static unsigned long long* g_tail_stamps = nullptr;   // snvrag_tail_stamps (diagnostics)
 unsigned long long* diag_stamps() { return g_tail_stamps; }
-
-template <int D>
-static int launch_tailp(TailArgs a, hipStream_t s) {
-  const long ntiles = cdiv(a.M, TL_ROWS);
-  const int grid = (int)std::min<long>(ntiles, cu_count());
-  a.desync = stagger_step(ntiles, 8L * grid, options().tail_desync, 25000 * D / 384 * D / 384);
-  constexpr size_t lds = (size_t)TP_NSLOT * SLAB_BYTES + 11 * D * 4;   // ring + [vec 8D | g1 | be1 | b_o]
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  auto kern = tailp_kernel<D>;
-  if (options().tail_variant == 7 && g_tail_stamps) {     // phase stamps (tools/tail_micro.py)
-    kern = tailp_kernel<D, true>;
-    a.stamps = g_tail_stamps;
-  }
-  return SNV_LAUNCH_LDS(kern, dim3((unsigned)grid), dim3(256), lds, s, a);
-}
 
 // the wide-row tail's first-round stagger (launch_tail below and snvrag_tail_qkv_forward)
 static int tailw_desync(int M) { return stagger_step(cdiv(M, TL_ROWS), 8 * 256, options().tail_desync, 10000); }
@@ -1101,22 +606,17 @@ static int launch_tail(TailArgs a, hipStream_t s) {
       // (tools/tailw_desync_sweep.py) but 0.7 % slower inside the bench step, 1.363 vs 1.353 ms,
       // profiles/r6_tail_desync_bench_ab.txt — 10 k kept)
       return tailw_launch(a.M, a.act, a.resid, a.out, a.ws, a.vec, a.b_o, a.g1, a.be1, a.eps, tailw_desync(a.M),
-                          (int)options().tail_wide >= 2 ? (int)options().tail_wide - 1 : 0, nullptr, nullptr,
-                          nullptr, s);
+                          options().tail_wide == 2 ? 1 : 0, nullptr, nullptr, nullptr, s);   // 2: phase stamps
     }
-  // the persistent kernel (option tail_persist; measured no faster, see tailp_kernel): 32-bit
-  // byte offsets of the in-place rows
-  if constexpr (PRE)
-    if ((var == 0 || var == 7) && options().tail_persist && (long)a.M * D * 2 < 0x7fffffffL) return launch_tailp<D>(a, s);
-  // default: 8 fragments read ahead (r5: 1.530 vs 1.553 ms at PF 4, mean of 5 sessions of
-  // tools/tail_micro.py at M = 527 360; variant 1 = PF 4, the r4 default)
-  auto kern = var == 1 ? tail_kernel<D, PRE, TL_PF4> : var == 2 ? tail_kernel<D, PRE, TL_PF4, 1>
-              : var == 3 ? tail_kernel<D, PRE, TL_PF4, 0, false>
-              : var == 5 ? tail_kernel<D, PRE, TL_PF4, 3> : tail_kernel<D, PRE, TL_PF_DEFAULT>;
-  if (var == 4 && D == 384 && g_tail_stamps) {           // phase stamps (tools/tail_micro.py)
-    kern = tail_kernel<D, PRE, TL_PF4, 2>;
-    a.stamps = g_tail_stamps;
-  }
+  // default: 8 fragments read ahead (r5: 1.530 vs 1.553 ms at 4, mean of 5 sessions of
+  // tools/tail_micro.py at M = 527 360).  tail_variant 4 with a stamp buffer: the stamped kernel
+  // (tools/tail_micro.py), which reads 4 ahead (see tail_kernel); any other value runs the default
+  auto kern = tail_kernel<D, PRE>;
+  if constexpr (D == 384)
+    if (var == 4 && g_tail_stamps) {
+      kern = tail_kernel<D, PRE, 0, true>;
+      a.stamps = g_tail_stamps;
+    }
   // first-round phase step: only when every CU runs several rounds (the delay is paid once).
   // Default 1/8 of a block's ~200 k cycles at D = 384 (tools/tail_micro.py, M = 527 360:
   // 1.668 ms without, 1.611 / 1.593 / 1.602 ms at 12 k / 25 k / 40 k), scaled with the D^2 work

@@ -195,7 +195,7 @@ struct TwArgs {
   const float* b_o; const float* g1; const float* be1;
   float eps;
   int desync;
-  unsigned long long* stamps;   // VAR 1: [workgroup][wave][8] s_memtime stamps
+  unsigned long long* stamps;   // STAMP: [workgroup][wave][8] s_memtime stamps
   int n_full;                   // workgroups of 128 rows (the rest: 32 rows)
   // the projection phase (null: none): qkv_out[M, 3 D] = out W^T + pbias, the next layer's QKV
   const char* pw;               // snvrag_proj_pack stream, NC = 3
@@ -287,15 +287,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t pw_out_rsrc(bf16* out, int M, 
 // MFMAs a step issues its W loads.  PROJ: the projection phase after LN2 (p.pw set): the tile's output
 // rows, in registers as bf16 when LN2 stores them, also go into the X images (LN1's layout for x1) and
 // are multiplied by the next layer's W_qkv (pw_chunks, NC = 3) — the rows never come back from HBM
-template <int VAR, int G, bool PROJ>
+template <bool STAMP, int G, bool PROJ>
 __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, const int wave) {
   constexpr int D = TW_D, NT = TW_NT, GI = G > 1 ? 1 : 0;
   constexpr uint32_t TW_PB = TW_H + 16 * 1024;        // LDS: the projection's bias table (3 D f32, 5 KiB of H half 0)
-  // VAR bit 3: the FFN epilogue in FFN2's MFMA gaps instead of FFN1's (A/B)
-  constexpr bool EPI_FFN2 = (VAR & 8) != 0;
-  // the residual rows loaded during phase A (after step TW_RES_STEP's W loads: the prologue's HBM
-  // burst halves, -2 k cycles per wave net, r6 tools/tailw_diag.py); VAR bit 4: in the prologue (A/B)
-  constexpr bool LATE_RES = (VAR & 16) == 0;
+  // the residual rows are loaded during phase A, after step TW_RES_STEP's W loads, not in the
+  // prologue: the prologue's HBM burst halves, -2 k cycles per wave net (r6)
   constexpr int TW_RES_STEP = 21;
   // s_nop ahead of the inline-asm MFMAs of a segment (TW_NOPMASK bit b, or the 32-row body)
   constexpr bool NOPA = G == 1 || (TW_NOPMASK & 1), NOP0 = G == 1 || (TW_NOPMASK & 2);
@@ -309,7 +306,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
   // used, so that the launch's v0 does not stay live through the bodies the kernel holds)
   unsigned long long st[8] = {};
   auto stamp = [&](int i) {
-    if constexpr (VAR & 1) st[i] = __builtin_amdgcn_s_memtime();
+    if constexpr (STAMP) st[i] = __builtin_amdgcn_s_memtime();
   };
   if (p.desync > 0 && blockIdx.x < 256) stagger_wait(p.desync);   // first-round stagger (mfma32.h)
   stamp(0);
@@ -337,10 +334,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
   // (compiler-visible loads: its waitcnt pass places the waits before every read of the register —
   // hand-counted asm loads were seen copied into AGPRs by the register allocator before they landed)
   const __amdgpu_buffer_rsrc_t wrb = __builtin_amdgcn_make_buffer_rsrc((void*)p.ws, (short)0, TW_NFRAG * FRAG_BYTES, 0x00020000);
-  // (diagnostic VAR bit 1: every load reads fragment F % 12 — a cache-resident 12 KiB, results wrong)
-  auto loadW = [&](u32x4& r, int F) {
-    r = __builtin_amdgcn_raw_buffer_load_b128(wrb, lane16, ((VAR & 2) ? F % 12 : F) * FRAG_BYTES, 0);
-  };
+  auto loadW = [&](u32x4& r, int F) { r = __builtin_amdgcn_raw_buffer_load_b128(wrb, lane16, F * FRAG_BYTES, 0); };
   // stream offsets: FFN1(h) step i = wave w's tile of chunk 4 (h >> 1) + w, half h & 1;
   // FFN2(h) step u, tile t = chunk 4 (h >> 1) + u / 2, k16 step 2 (h & 1) + u % 2, tile 3w + t
   auto f_ffn1 = [&](int h, int i) { return TW_FPRE + (4 * (h >> 1) + wave) * TW_FPC + 2 * i + (h & 1); };
@@ -357,8 +351,8 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
   };
   unroll([&](auto nc) { issue_a(nc); }, std::make_integer_sequence<int, TW_AH>{});
   u32x4 rr[3][4][2];                                 // residual x: tile t, group g, half h2
-  // (LATE_RES: issued after phase A step TW_RES_STEP's W loads instead of here — the prologue's HBM
-  // burst halves; the W waits after it then also wait for these rows, in-order vmcnt)
+  // (issued after phase A step TW_RES_STEP's W loads; the W waits after it then also wait for these
+  // rows, in-order vmcnt)
   auto load_res = [&]() {
     const int l = lane_id();
 #pragma unroll
@@ -372,7 +366,6 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
           rr[t][g][h2] = *reinterpret_cast<const u32x4*>(p.resid + r * D + 32 * (3 * wave + t) + 16 * (l >> 5) + 8 * h2);
     }
   };
-  if constexpr (!LATE_RES) load_res();
   float* tab = reinterpret_cast<float*>(smem + TW_H);                        // [b_o | g1 | be1]
   for (int i = 64 * wave + lane_id(); i < D; i += 256) {
     tab[i] = p.b_o[i];
@@ -380,14 +373,6 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
     tab[2 * D + i] = p.be1[i];
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  // the residual rows retired here (else the compiler's wait for them lands at LN1, behind the
-  // in-flight W loads of the first FFN steps)
-  if constexpr (!LATE_RES) {
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int g = 0; g < G; ++g) asm volatile("" : "+v"(rr[t][g][0]), "+v"(rr[t][g][1]));
-  }
   tw_barrier();
   stamp(1);
 
@@ -417,7 +402,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
         unroll([&](auto tc) { issue_a(std::integral_constant<int, n0 + TW_AH + decltype(tc)::value>{}); },
                   std::make_integer_sequence<int, 3>{});
     }
-    if constexpr (LATE_RES && q == TW_RES_STEP) load_res();
+    if constexpr (q == TW_RES_STEP) load_res();
     __builtin_amdgcn_sched_barrier(0);
   }, std::make_integer_sequence<int, TW_QA>{});
   tw_drain_o(acc);
@@ -609,9 +594,9 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
   };
   // FFN1(h), parity P; Q0 = its first global step (the representative half-round for h >= 1);
   // EPI: with the epilogue of half-round h - 1 (unit k over steps 3k .. 3k + 2, one piece per MFMA gap)
-  auto seg1 = [&](int h, auto p_tag, auto q0_tag, auto epi_tag, auto nop_tag, auto b1_tag) {
+  auto seg1 = [&](int h, auto p_tag, auto q0_tag, auto epi_tag, auto nop_tag) {
     constexpr int P = decltype(p_tag)::value, Q0 = decltype(q0_tag)::value;
-    constexpr bool EPI = decltype(epi_tag)::value, NOP = decltype(nop_tag)::value, B1 = decltype(b1_tag)::value;
+    constexpr bool EPI = decltype(epi_tag)::value, NOP = decltype(nop_tag)::value;
     constexpr int F0 = tw_f0(Q0);
     unroll([&](auto ic) {
       constexpr int i = decltype(ic)::value, q = Q0 + i, n = F0 + i;
@@ -625,8 +610,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
           if constexpr (i == 0) mfma32_asm0<true, NOP>(ha[g], wf[n % TW_RING], bq[(i + 2) % 3][g]);
           else mfma32_asm<true, NOP>(ha[g], wf[n % TW_RING], bq[(i + 2) % 3][g]);
         }
-        // (diagnostic VAR bit 2: FFN1 reads no B fragments — stale operands, no LDS traffic)
-        if constexpr (i + 2 < 24 && !(VAR & 4)) bq[(i + 4) % 3][g] = rdB(TW_X, (i + 2) * 4 + g);
+        if constexpr (i + 2 < 24) bq[(i + 4) % 3][g] = rdB(TW_X, (i + 2) * 4 + g);
         if constexpr (g == GI) {
           if constexpr (Q0 == TW_QA) issue_a(std::integral_constant<int, n + TW_AH>{});
           else issue_it(std::integral_constant<int, i + TW_AH>{}, h, std::false_type{});
@@ -638,7 +622,6 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
         }
       }, std::make_integer_sequence<int, G>{});
       if constexpr (Q0 == TW_QA && i == 16) b1_load(0);
-      if constexpr (B1 && i == 8) b1_load(h);        // for this half-round's epilogue in the next FFN2
       __builtin_amdgcn_sched_barrier(0);
     }, std::make_integer_sequence<int, 24>{});
     if constexpr (P == 0) tw_drain_h4<false>(hv);
@@ -646,14 +629,11 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
   };
   // FFN2(h) from H half h & 1 (P = h & 1); in the loop (Q0 = representative) its iteration is h + 1;
   // LAST: the iteration of h = 10, whose lookahead loads FFN2(11); FINAL: FFN2(11) itself
-  // EPI: with the epilogue of half-round h + 1 (whose FFN1 ran just before; parity 1 - P), one piece
-  // after each of the 24 G MFMAs (unit k over gaps 3 G k .. 3 G k + 3 G - 1)
-  // (FFN1-gap schedule: b1 of half-round h + 1 loaded at step 0, for its epilogue in FFN1(h + 2))
-  auto seg2 = [&](int h, auto p_tag, auto q0_tag, auto last_tag, auto final_tag, auto nop_tag, auto epi_tag) {
+  // (b1 of half-round h + 1 is loaded at step 0, for its epilogue in FFN1(h + 2))
+  auto seg2 = [&](int h, auto p_tag, auto q0_tag, auto last_tag, auto final_tag, auto nop_tag) {
     constexpr int P = decltype(p_tag)::value, Q0 = decltype(q0_tag)::value;
     constexpr bool LAST = decltype(last_tag)::value, FINAL = decltype(final_tag)::value;
-    constexpr bool NOP = decltype(nop_tag)::value, EPI = decltype(epi_tag)::value;
-    constexpr bool B1N = !EPI && !FINAL && !EPI_FFN2;
+    constexpr bool NOP = decltype(nop_tag)::value;
     constexpr uint32_t HB = TW_H + P * 32768;
     constexpr int F0 = tw_f0(Q0);
 #pragma unroll
@@ -667,13 +647,8 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
       unroll([&](auto gc) {
         constexpr int g = decltype(gc)::value;
         unroll([&](auto tc) {
-          constexpr int t = decltype(tc)::value, x = 3 * G * u + 3 * g + t;
+          constexpr int t = decltype(tc)::value;
           mfma32_asm<true, NOP>(acc[t][g], wf[(n0 + t) % TW_RING], bq[u % 3][g]);
-          if constexpr (EPI) {
-            epi_piece(std::integral_constant<int, x / (3 * G)>{}, std::integral_constant<int, 1 - P>{},
-                      std::integral_constant<int, x % (3 * G)>{});
-            __builtin_amdgcn_sched_barrier(0);
-          }
         }, std::make_integer_sequence<int, 3>{});
         if constexpr (u + 2 < 8) bq[(u + 2) % 3][g] = rdB(HB, (u + 2) * 4 + g);
         else if constexpr (!FINAL && !LAST) bq[(u + 2) % 3][g] = rdB(TW_X, (u - 6) * 4 + g);   // next FFN1 steps 0, 1
@@ -691,7 +666,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
           }
         }
       }, std::make_integer_sequence<int, G>{});
-      if constexpr (B1N && u == 0) b1_load(h + 1);
+      if constexpr (!FINAL && u == 0) b1_load(h + 1);
       __builtin_amdgcn_sched_barrier(0);
     }, std::make_integer_sequence<int, 8>{});
     tw_drain_o(acc);
@@ -701,8 +676,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
     bq[2][g] = rdB(TW_X, g);
     bq[0][g] = rdB(TW_X, 4 + g);
   }
-  seg1(0, std::integral_constant<int, 0>{}, std::integral_constant<int, TW_QA>{}, std::false_type{}, TNA{},
-       std::false_type{});
+  seg1(0, std::integral_constant<int, 0>{}, std::integral_constant<int, TW_QA>{}, std::false_type{}, TNA{});
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     bq[2][g] = rdB(TW_X, g);
@@ -714,9 +688,9 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
   using IQ2 = std::integral_constant<int, TW_QREP + 24>;
   using P0 = std::integral_constant<int, 0>;
   using P1 = std::integral_constant<int, 1>;
-  // a barrier of the FFN (stamped variants: cycles parked in the FFN's barriers into stamp slot 6)
+  // a barrier of the FFN (the stamped kernel: cycles parked in the FFN's barriers into stamp slot 6)
   auto ffn_barrier = [&]() {
-    if constexpr (VAR & 1) {
+    if constexpr (STAMP) {
       const unsigned long long t0 = __builtin_amdgcn_s_memtime();
       tw_barrier();
       st[6] += __builtin_amdgcn_s_memtime() - t0;
@@ -724,47 +698,25 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
       tw_barrier();
     }
   };
-  if constexpr (!EPI_FFN2) {
-    // FFN1(h) with the epilogue of half-round h - 1 in its MFMA gaps (b1(h - 1) loaded at FFN2(h - 2)
-    // step 0), barrier, FFN2(h - 1)
+  // FFN1(h) with the epilogue of half-round h - 1 in its MFMA gaps (b1(h - 1) loaded at FFN2(h - 2)
+  // step 0), barrier, FFN2(h - 1)
 #pragma unroll 1
-    for (int h = 1; h < 11; h += 2) {
-      seg1(h, P1{}, IQR{}, T1{}, T0{}, T0{});
-      ffn_barrier();                                  // H half (h - 1) & 1 complete
-      seg2(h - 1, P0{}, IQ2{}, T0{}, T0{}, T0{}, T0{});
-      seg1(h + 1, P0{}, IQR{}, T1{}, T0{}, T0{});
-      ffn_barrier();
-      seg2(h, P1{}, IQ2{}, T0{}, T0{}, T0{}, T0{});
-    }
-    seg1(11, P1{}, IQR{}, T1{}, TNT{}, T0{});
+  for (int h = 1; h < 11; h += 2) {
+    seg1(h, P1{}, IQR{}, T1{}, T0{});
+    ffn_barrier();                                    // H half (h - 1) & 1 complete
+    seg2(h - 1, P0{}, IQ2{}, T0{}, T0{}, T0{});
+    seg1(h + 1, P0{}, IQR{}, T1{}, T0{});
     ffn_barrier();
-    seg2(10, P0{}, IQ2{}, T1{}, T0{}, TNT{}, T0{});
-    // the epilogue of half-round 11, then its FFN2
-    unroll([&](auto kc) {                          // (unit by unit: a unit's pieces share ex / epk)
-      unroll([&](auto pc) { epi_piece(kc, P1{}, pc); }, std::make_integer_sequence<int, TW_EP>{});
-    }, std::make_integer_sequence<int, 8>{});
-    ffn_barrier();
-  } else {
-    // FFN1(1) with the epilogue of half-round 0 in its MFMA gaps (no FFN2 to carry it yet); then b1
-    // of half-round 1 (after the epilogue's last read of b1v)
-    seg1(1, P1{}, std::integral_constant<int, TW_Q0>{}, T1{}, TNT{}, T0{});
-    b1_load(1);
-    ffn_barrier();                                    // H half 0 complete
-    // FFN2(h - 1) with the epilogue of half-round h in its MFMA gaps, FFN1(h + 1) (pure MFMA +
-    // B-fragment reads), one barrier (H half h & 1 complete): the same W consumption order
-#pragma unroll 1
-    for (int h = 1; h < 11; h += 2) {
-      seg2(h - 1, P0{}, IQ2{}, T0{}, T0{}, T0{}, T1{});
-      seg1(h + 1, P0{}, IQR{}, T0{}, T0{}, T1{});
-      ffn_barrier();
-      seg2(h, P1{}, IQ2{}, T0{}, T0{}, T0{}, T1{});
-      seg1(h + 2, P1{}, IQR{}, T0{}, T0{}, T1{});
-      ffn_barrier();
-    }
-    // FFN2(10) with the epilogue of half-round 11, then FFN2(11)
-    seg2(10, P0{}, IQ2{}, T1{}, T0{}, TNT{}, T1{});
-    ffn_barrier();
+    seg2(h, P1{}, IQ2{}, T0{}, T0{}, T0{});
   }
+  seg1(11, P1{}, IQR{}, T1{}, TNT{});
+  ffn_barrier();
+  seg2(10, P0{}, IQ2{}, T1{}, T0{}, TNT{});
+  // the epilogue of half-round 11, then its FFN2
+  unroll([&](auto kc) {                            // (unit by unit: a unit's pieces share ex / epk)
+    unroll([&](auto pc) { epi_piece(kc, P1{}, pc); }, std::make_integer_sequence<int, TW_EP>{});
+  }, std::make_integer_sequence<int, 8>{});
+  ffn_barrier();
   // H half 0 is free from here (its last reader, FFN2(10), is behind this barrier): the LN epilogue's
   // tables [b2' | c1 | g2 | be2] (6 KiB) arrive there by LDS-DMA during FFN2(11) (retired by the
   // vmcnt(0) after it, visible after the epilogue's first barrier)
@@ -784,7 +736,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
     }
   }
   seg2(11, std::integral_constant<int, 1>{}, std::integral_constant<int, TW_QF>{}, std::false_type{},
-       std::true_type{}, TNF{}, std::false_type{});
+       std::true_type{}, TNF{});
   float st1[4], st2[4];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
@@ -970,7 +922,7 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
     pw_chunks<G, NOPP>(smem, lds0 + TW_PB, wave, lane16, pwb, 3, pw_out_rsrc(p.qkv_out, p.M, row0, 3), wf, acc);
     stamp(7);
   }
-  if constexpr (VAR & 1) {
+  if constexpr (STAMP) {
     if (lane_id() == 0 && p.stamps) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) p.stamps[((long)blockIdx.x * 4 + wave) * 8 + i] = st[i];
@@ -980,27 +932,24 @@ __device__ __forceinline__ void tailw_body(const TwArgs& p, const long row0, con
 
 // workgroups [0, n_full): 128-row tiles; the rest: 32-row tiles after row 128 n_full (the launch's
 // last partial round of 128-row tiles spread over 4x the CUs, dispatched last)
-template <int VAR>
+template <bool STAMP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void tailw_kernel(TwArgs p) {
-  // with a projection stream (the default and the stamped instantiation only): the bodies with the
-  // projection phase — a tile's rows never need a second kernel, the 32-row tiles included
+  // with a projection stream: the bodies with the projection phase — a tile's rows never need a
+  // second kernel, the 32-row tiles included
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if constexpr (VAR <= 1) {
-    if (p.pw) {
-      if ((int)blockIdx.x < p.n_full) tailw_body<VAR, 4, true>(p, (long)blockIdx.x * 128, wave);
-      else tailw_body<VAR, 1, true>(p, (long)p.n_full * 128 + (long)(blockIdx.x - p.n_full) * 32, wave);
-      return;
-    }
+  if (p.pw) {
+    if ((int)blockIdx.x < p.n_full) tailw_body<STAMP, 4, true>(p, (long)blockIdx.x * 128, wave);
+    else tailw_body<STAMP, 1, true>(p, (long)p.n_full * 128 + (long)(blockIdx.x - p.n_full) * 32, wave);
+    return;
   }
-  if ((int)blockIdx.x < p.n_full) tailw_body<VAR, 4, false>(p, (long)blockIdx.x * 128, wave);
-  else tailw_body<VAR, 1, false>(p, (long)p.n_full * 128 + (long)(blockIdx.x - p.n_full) * 32, wave);
+  if ((int)blockIdx.x < p.n_full) tailw_body<STAMP, 4, false>(p, (long)blockIdx.x * 128, wave);
+  else tailw_body<STAMP, 1, false>(p, (long)p.n_full * 128 + (long)(blockIdx.x - p.n_full) * 32, wave);
 }
 
 int tailw_launch(int M, const void* att, const void* resid, void* out, const void* ws, const float* vec,
                  const float* b_o, const float* g1, const float* be1, float eps, int desync, int var,
                  const void* pw, const float* pbias, void* qkv_out, hipStream_t s) {
-  if (pw && (var & ~1)) return fail(__func__, "the projection phase runs in the default and the stamped tail only");
   // the last partial round of 128-row tiles (rem of 256 CUs) as 4 rem workgroups of 32 rows, when
   // they fit one round of 32-row tiles (option tail_split = the largest rem split; 0: off)
   const long T = cdiv(M, 128), rem = T % 256;
@@ -1009,16 +958,11 @@ int tailw_launch(int M, const void* att, const void* resid, void* out, const voi
   const long nwg = n_full < T ? n_full + cdiv((long)M - n_full * 128, 32) : T;
   TwArgs a{M, (const bf16*)att, (const bf16*)resid, (bf16*)out, (const char*)ws, vec, b_o, g1, be1, eps, desync,
            diag_stamps(), (int)n_full, (const char*)pw, pbias, (bf16*)qkv_out};
-  // var (option tail_wide - 1): bit 0 phase stamps, bit 1 / bit 2 the W-latency / FFN1-LDS
-  // diagnostics (wrong results: tools/tailw_diag.py timing only; r6: W-cached no faster, no-FFN1-LDS
-  // 2 %), bit 3 the FFN epilogue in FFN2's gaps (A/B)
-  if ((var & 1) && !a.stamps) var &= ~1;
-  auto kern = var == 1 ? tailw_kernel<1> : var == 2 ? tailw_kernel<2> : var == 4 ? tailw_kernel<4>
-              : var == 8 ? tailw_kernel<8> : var == 9 ? tailw_kernel<9> : var == 16 ? tailw_kernel<16>
-              : var == 17 ? tailw_kernel<17> : tailw_kernel<0>;
+  // var (option tail_wide - 1): bit 0 = phase stamps, with a snvrag_tail_stamps buffer; the other
+  // bits select nothing
+  auto kern = (var & 1) && a.stamps ? tailw_kernel<true> : tailw_kernel<false>;
   return SNV_LAUNCH_LDS(kern, dim3((unsigned)nwg), dim3(256), TW_LDS, s, a);
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // Wide-row projection (option proj_wide; the encoder's QKV: out[M, NC D] = x W^T + b, D = 384,

@@ -656,15 +656,15 @@ def test_attention_dh32_variants_bit_identical(L):
 
 
 @pytest.mark.parametrize("M", [1, 777, 128 * 256 + 5, 64 * 1030])
-def test_tail_persistent_equals_tail_kernel(M):
-    """The persistent block tail (tailp_kernel: one workgroup per CU over 128-row tiles, the
-    activations streamed into the weight ring; option tail_persist) == tail_kernel to one bf16
-    rounding step on at most 0.1 % of the outputs (the same arithmetic), in place, and the default
-    tail_kernel (8 fragments read ahead) == its 4-fragment variant bit for bit, incl. a ragged last tile, a single partial tile
-    and 515 tiles (two per workgroup for most CUs, every chunk rotation)."""
+def test_tail_kernel_384_vs_fp64(M):
+    """tail_kernel<384, PRE> (csrc/tail.hip; option tail_wide 0, since snvrag_tail_forward at D = 384
+    runs the wide-row tail by default) in place vs float64 torch on the same bf16 operands, with
+    test_tail32_kernel's bar; and two launches on the same inputs give the same bits (the kernel has
+    no atomics).  A single partial tile, a ragged last tile, 257 tiles (a second round of 128-row
+    workgroups with a 5-row tile) and 515 tiles (every chunk rotation of the stream)."""
     D = 384
     g = torch.Generator(device="cpu").manual_seed(M)
-    bf = torch.bfloat16
+    bf, F = torch.bfloat16, torch.nn.functional
     x = torch.randn(M, D, generator=g).to(DEV, bf)
     att = (0.5 * torch.randn(M, D, generator=g)).to(DEV, bf)
     w_o = (torch.randn(D, D, generator=g) / math.sqrt(D)).to(DEV, bf)
@@ -678,23 +678,20 @@ def test_tail_persistent_equals_tail_kernel(M):
     w2g, b2g, _ = K().fold_layernorm(w2, b2, gf, bff, bf)
     vec = K().ffn_vec(b1, b2g, w2g, g2, be2)
     ts = K().tail_pack(w_o, w1, w2g)
-    ya, yb, yc = x.clone(), x.clone(), x.clone()
-    with K().option("tail_wide", 0):                     # (the engine's default is the wide-row tail)
-        with K().option("tail_persist", 1):
-            K().tail_forward(att, ya, ts, b_o, g1, be1, vec)
+    x1 = F.layer_norm(x.double() + att.double() @ w_o.double().T + b_o.double(), (D,), g1.double(), be1.double(), 1e-5)
+    h = F.leaky_relu(x1 @ w1.double().T + b1.double(), 0.1)
+    hn = F.layer_norm(h, (4 * D,), gf.double(), bff.double(), 1e-5)
+    f = F.leaky_relu(hn @ w2.double().T + b2.double(), 0.1)
+    ref = F.layer_norm(x1 + f, (D,), g2.double(), be2.double(), 1e-5)
+    ya, yb = x.clone(), x.clone()
+    with K().option("tail_wide", 0):
+        out = K().tail_forward(att, ya, ts, b_o, g1, be1, vec)
         K().tail_forward(att, yb, ts, b_o, g1, be1, vec)
-        with K().option("tail_variant", 1):              # tail_kernel with 4 fragments read ahead
-            K().tail_forward(att, yc, ts, b_o, g1, be1, vec)
-    assert torch.equal(yb, yc)
+    assert out.data_ptr() == ya.data_ptr()
     assert torch.isfinite(ya.float()).all()
-    # the same arithmetic; the compilers' f32 contraction choices in the LayerNorm statistics may
-    # differ, which moves a handful of outputs by one bf16 rounding step (measured: one feature in
-    # ~2 % of rows)
-    d = (ya.float() - yb.float()).abs()
-    # (one bf16 step of the value, or of a ~1e-3 value for outputs near zero)
-    ulp = yb.float().abs().clamp_min(2 ** -10) * 2 ** -7
-    assert bool((d <= ulp * 1.01).all()), float((d / ulp).max())
-    assert int((d > 0).sum()) <= max(8, ya.numel() // 1000), int((d > 0).sum())
+    torch.testing.assert_close(ya.double(), ref, rtol=5e-2, atol=5e-2)
+    assert (ya.double() - ref).abs().mean() < 1e-2
+    assert torch.equal(ya, yb)
 
 
 def _bf16_step(x: torch.Tensor) -> torch.Tensor:
@@ -916,16 +913,10 @@ def _rn(g):
 
 def _stagger_tail(entry):
     kk, D, bf, F = K(), 384, torch.bfloat16, torch.nn.functional
-    if entry == "persist":
-        # csrc/tail.hip launch_tailp `ntiles >= 8L * grid` (grid = one workgroup per CU) and
-        # tailp_kernel's `ntiles % G != 0` (only the workgroups with one tile fewer wait)
-        ntiles = 8 * _n_cu() + 5
-        assert ntiles >= 8 * _n_cu() and ntiles % _n_cu() != 0
-    else:
-        # csrc/tail.hip launch_tail `nwg >= 8 * 256`: the wide-row launch (tail_wide = 1) and
-        # tail_kernel (tail_wide = 0; the FFN-only entry takes the same line)
-        ntiles = 8 * 256
-        assert ntiles >= 8 * 256
+    # csrc/tail.hip launch_tail `nwg >= 8 * 256`: the wide-row launch (tail_wide = 1) and
+    # tail_kernel (tail_wide = 0; the FFN-only entry takes the same line)
+    ntiles = 8 * 256
+    assert ntiles >= 8 * 256
     M = 128 * (ntiles - 1) + 77
     rn = _rn(torch.Generator(device=DEV).manual_seed(M))
     x, att = rn(M, D).to(bf), rn(M, D, sc=0.5).to(bf)
@@ -942,7 +933,7 @@ def _stagger_tail(entry):
     def run():
         if entry == "ffn":
             return kk.tail_ffn_forward(x, ts, vec)
-        with kk.option("tail_wide", int(entry == "wide")), kk.option("tail_persist", int(entry == "persist")):
+        with kk.option("tail_wide", int(entry == "wide")):
             return kk.tail_forward(att, x.clone(), ts, b_o, g1, be1, vec)
 
     def check(out, rows):                               # test_tail32_kernel / test_tail_wide_kernel's bar
@@ -1073,7 +1064,7 @@ def _stagger_projw():
 
 _STAGGER = {
     "tail_wide": lambda: _stagger_tail("wide"), "tail": lambda: _stagger_tail("tail"),
-    "tail_ffn": lambda: _stagger_tail("ffn"), "tail_persist": lambda: _stagger_tail("persist"),
+    "tail_ffn": lambda: _stagger_tail("ffn"),
     "sgemm_ln_4w": lambda: _stagger_sgemm(4), "sgemm_8w": lambda: _stagger_sgemm(8),
     "mlp": lambda: _stagger_mlp(False), "mlp_afgate": lambda: _stagger_mlp(True),
     "gemm256": lambda: _stagger_gemm256(False), "gemm256_ln": lambda: _stagger_gemm256(True),

@@ -20,7 +20,7 @@ READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
 
 # (demangled-name prefix, what runs it)
 HOT = [
-    ("snvrag::tail_kernel<384, true, 4, 0, true, 0>", "block tail (bench roofline kernel)"),
+    ("snvrag::tail_kernel<384, true, 0, false>", "block tail (bench roofline kernel)"),
     ("snvrag::attn32_dma<true, false, 0>", "inference attention"),
     ("snvrag::attn32_dma<false, true, 0>", "training attention forward"),
     ("snvrag::attn_bwd_dkv32", "training attention backward dK/dV"),
@@ -33,7 +33,7 @@ HOT = [
     ("snvrag::g3_kernel<7, 0, 0>", "training wide-row GEMM (M = 49 440)"),
     ("snvrag::g3_kernel<6, 0, 1>", "rag fusion K = 4D projection + LN / MAF tail (bench M)"),
     ("snvrag::g3_kernel<7, 0, 1>", "rag fusion K = 4D projection + LN / MAF tail"),
-    ("snvrag::tailw_kernel<0>", "wide-row block tail (bench roofline kernel)"),
+    ("snvrag::tailw_kernel<false>", "wide-row block tail (bench roofline kernel)"),
     ("snvrag::dw_dma_kernel", "training dW"),
     ("snvrag::scan2_kernel<16, 2, 0>", "kNN panel scan"),
     # (bf16 template arguments: c++filt leaves these names mangled)

@@ -1,11 +1,8 @@
-"""Where the wide-row block tail's cycles go (csrc/tailw.hip diagnostic instantiations; timing only,
-their outputs are wrong): launch times at the bench shape (M = 512 x 1030) of
-  base        tailw_kernel<0>
-  W-cached    every W fragment load reads a 12 KiB cache-resident slice (bit 1: no L2-miss / HBM
-              latency or L2 bandwidth in the weight stream)
-  no-FFN1-LDS FFN1 steps read no B fragments (bit 2: FFN1 without its LDS traffic)
-  both
-and each one's per-wave phase stamps."""
+"""Where the wide-row block tail's cycles go (csrc/tailw.hip): launch times at the bench shape
+(M = 512 x 1030) of
+  base        tailw_kernel, the last partial round split into 32-row tiles (option tail_split 64)
+  no-split    the same kernel with tail_split 0
+and each one's per-wave phase stamps (the stamped instantiation, tail_wide = 2)."""
 import os
 import sys
 
@@ -22,9 +19,7 @@ D = 384
 M = int(os.environ.get("GM_M", 512 * 1030))
 c = case(M, 1)
 ts = K.tail_pack(c["w_o"], c["w1"], c["w2g"])
-VARS = {"base": (1, 64), "early-resid": (17, 64), "no-split": (1, 0)}
-if os.environ.get("DIAG_ALL"):
-    VARS.update({"W-cached": (3, 64), "no-FFN1-LDS": (5, 64)})
+VARS = {"base": (1, 64), "no-split": (1, 0)}
 
 
 def timeit(optv, reps=10):
@@ -47,7 +42,7 @@ def timeit(optv, reps=10):
 
 for _ in range(20):
     timeit((1, 64), 1)
-# correctness of the A/B arms (same arithmetic: bitwise equal outputs)
+# the split changes the launch shape only: bitwise equal outputs
 outs = {}
 for name, (opt, split) in VARS.items():
     xs = c["x"].clone()

@@ -16,7 +16,7 @@ D = 384
 dev, bf = "cuda", torch.bfloat16
 F = torch.nn.functional
 sys.path.insert(0, os.path.dirname(__file__))
-from tailw_micro_case import case, ref  # noqa: E402
+from tailw_micro_case import case, ref, run  # noqa: E402
 
 
 for M in (777, 128, 1, 4 * 1030 + 5):
@@ -90,7 +90,7 @@ for wide in (0, 1):
           flush=True)
 
 # phase stamps (tail_wide = 2)
-nwg = (M + 127) // 128
+nwg = (M + 31) // 32                                   # >= the workgroups of a split launch (option tail_split)
 st = torch.zeros(nwg * 4 * 8, dtype=torch.int64, device=dev)
 N.lib().snvrag_tail_stamps(st.data_ptr())
 for _ in range(10):
@@ -100,7 +100,9 @@ K.tail_forward(c["att"], xs, ts, c["b_o"], c["g1"], c["be1"], c["vec"])
 torch.cuda.synchronize()
 K.set_option("tail_wide", 0)
 N.lib().snvrag_tail_stamps(None)
-s = st.view(nwg * 4, 8).cpu().numpy().astype(np.float64)
+n_full = (M + 127) // 128
+n_full = n_full - n_full % 256 if (n_full > 256 and 0 < n_full % 256 <= 64) else n_full
+s = st.view(nwg * 4, 8)[:n_full * 4].cpu().numpy().astype(np.float64)    # the 128-row workgroups
 names = ["prologue (att DMA, residual, tables)", "out-projection (288 MFMA)", "LN1 (2 barriers)",
          "FFN 6 rounds (2304 MFMA)", "LN_f + LN2 + stores"]
 tot = s[:, 5] - s[:, 0]
