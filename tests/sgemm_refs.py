@@ -184,7 +184,8 @@ def act(x, w, b, act="none", rank=None, g=None):
     return SimpleNamespace(out=y, bound=bf16_ulp(y) / 2 + dy, z=p.z, dz=p.dz)
 
 
-def _ln_tail(v, dv, g, be, eps):
+def _ln_tail(v, dv, g, be, eps, half=True):
+    """LayerNorm of the un-rounded v (error dv); half: the output is rounded to bf16."""
     D = v.shape[1]
     d = D // 2 + 1
     g, be = _d(g).to(v.device), _d(be).to(v.device)
@@ -197,7 +198,7 @@ def _ln_tail(v, dv, g, be, eps):
             + 2 * mean.abs() * dm + 3 * U * mean * mean)
     dr = rstd * (0.5 * dvar / (var + eps) + (3 + C["sqrt"] + C["div"]) * U)
     Ay = g.abs() * rstd * (v.abs() + mean.abs()) + be.abs()
-    by = bf16_ulp(y) / 2 + g.abs() * (rstd * (dv + dm) + (v - mean).abs() * dr) + C["ln"] * U * Ay
+    by = (bf16_ulp(y) / 2 if half else 0.0) + g.abs() * (rstd * (dv + dm) + (v - mean).abs() * dr) + C["ln"] * U * Ay
     return SimpleNamespace(out=y, bound=by, mean=mean, var=var, rstd=rstd)
 
 
