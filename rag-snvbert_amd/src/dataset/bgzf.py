@@ -143,6 +143,7 @@ class BgzfWriter:
 
     def __init__(self, path, block_size: int = 0xff00, level: int = 6):
         self.fh, self.block_size, self.level, self.buf = open(path, "wb"), block_size, level, bytearray()
+        self.eof_virtual = None
 
     def write(self, data) -> int:
         self.buf += data
@@ -151,9 +152,17 @@ class BgzfWriter:
             del self.buf[:self.block_size]
         return len(data)
 
+    def tell_virtual(self) -> int:
+        """The virtual offset of the next byte written: the file offset of the member being filled ``<< 16`` and
+        the bytes buffered in it (fewer than ``block_size``: a full member has left, so a position on a member
+        boundary has offset 0 in the later member).  After ``close``: the EOF block's offset ``<< 16``."""
+        return self.fh.tell() << 16 | len(self.buf) if self.eof_virtual is None else self.eof_virtual
+
     def close(self) -> None:
         if self.buf:
             self.fh.write(bgzf_member(bytes(self.buf), self.level))
+            self.buf = bytearray()
+        self.eof_virtual = self.fh.tell() << 16
         self.fh.write(EOF_BLOCK)
         self.fh.close()
 

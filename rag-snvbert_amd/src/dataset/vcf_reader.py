@@ -35,14 +35,24 @@ tail straight into the text buffer, the chunk is cut at its last newline by a de
 index, parse and pack steps run unchanged.  Only the few blocks that hold the header are inflated on the host.
 A file that is not BGZF (plain text, a single-member gzip) takes the host path with one line of notice.
 
-Not covered: single-member gzip on the device, ``.csi`` / ``.tbi`` random access and index output (BGZF
-output is ``write_vcf_device(bgzf=True)`` / ``--vcf_bgzf``), a rank reading only its shard's sample columns, multi-allelic splitting (any allele number > 0 is
+``region=(name, first, last)`` reads the records of one sequence with ``first <= POS <= last`` through the
+file's tabix index ``path + ".tbi"`` (``tbi.py``; both VCF writers produce one with ``index=True`` /
+``--vcf_index``): the header comes from the front of the file, ``tbi.query`` gives one span of virtual offsets, and
+only the raw bytes of the members that span touches are read, inflated (either mode) and parsed.  Selection is
+by POS, not by overlap: REF is not parsed, so a record that begins in front of ``first`` and reaches into the
+region is not returned.  ``READ_STATS`` counts the members the last call inflated.
+
+Not covered: single-member gzip on the device, ``.csi`` indexes, overlap (REF-length) selection of a region, an
+indexer on the device for files this project did not write (``tbi.index_vcf_bgzf`` is the slow host
+specification), a rank reading only its shard's sample columns, multi-allelic splitting (any allele number > 0 is
 ALT), REF / ALT / ID strings, h5 files.
 """
 
 from __future__ import annotations
 
+import contextlib
 import gzip
+import io
 import os
 from dataclasses import dataclass
 from typing import List, Tuple, Union
@@ -64,6 +74,8 @@ INFLATE_MODES = ("host", "device")
 DEFAULT_INFLATE = "host"               # what read_vcf(inflate=None) does; set_default_inflate changes it
 MAX_CHUNK_BLOCKS = 1 << 16             # BGZF blocks per chunk of the device inflate (empty blocks are legal)
 RAW_PIECE = 1 << 20                    # raw file bytes per read of the device inflate
+SMALL_SPAN = 32 << 20                  # a region's raw bytes up to here are read at once and size its buffers
+READ_STATS = {"members_inflated": 0}   # of the last read_vcf of a BGZF file by its member table (header members too)
 
 
 def set_default_inflate(mode: str) -> None:
@@ -241,9 +253,12 @@ class _ChunkParser:
     """What follows a chunk's text on the device, for either source of the text: line index, parse, and the
     pack of every whole group of 64 records; ``finish`` joins the parts."""
 
-    def __init__(self, path, name, dev, samples, chunk_bytes, force_general):
+    def __init__(self, path, name, dev, samples, chunk_bytes, force_general, region=None):
         import torch
         self.path, self.name, self.dev, self.samples, self.force_general = path, name, dev, samples, force_general
+        # a region read: the records kept per chunk (count, their line offsets, the chunk's place in the span's
+        # text) and the span's members (file offset, ISIZE), for the virtual offset an error message names
+        self.region, self.kept, self.members, self.text_base = region, [], [], 0
         self.S = S = len(samples)
         # a record holds at least 8 one-byte columns, GT and S one-byte cells, each with its separator
         self.max_lines = chunk_bytes // (2 * S + 17) + 1
@@ -267,10 +282,14 @@ class _ChunkParser:
         line_off, n_lines = K.vcf_line_index(text, cut, self.max_lines)
         nl = int(n_lines.item())                       # also: the chunk's upload has left the host
         if nl > self.max_lines:                        # a line shorter than any record
-            parse_vcf_host(self.path)
+            if self.region is None:                    # (a region read does not scan the file for the line)
+                parse_vcf_host(self.path)
             raise ValueError(f"{self.name}: a body line is shorter than a record of {self.S} samples")
         if nl:
             p, f = K.vcf_parse_gt(text, cut, line_off, nl, self.S, self.codes[self.carry:], self.force_general)
+            if self.region is not None:
+                p, f, nl = self._select(p, f, line_off, nl)
+        if nl:
             self.pos_parts.append(p)
             self.flag_parts.append(f)
         parsed_event.record(stream)
@@ -284,6 +303,36 @@ class _ChunkParser:
         else:
             self.carry = total
         self.n_records += nl
+
+    def _select(self, p, f, line_off, nl):
+        """Drop the records the span brought in outside [first, last]: positions are sorted inside a sequence,
+        so those are a prefix and a suffix of the chunk, and the kept code rows move to the front of the chunk's."""
+        _, first, last = self.region
+        pos = p.cpu().numpy()
+        hit = np.flatnonzero((pos >= first) & (pos <= last))
+        lo, hi = (int(hit[0]), int(hit[-1]) + 1) if hit.size else (0, 0)
+        if hit.size != hi - lo:
+            raise ValueError(f"{self.name}: the positions between POS {int(pos[lo])} and {int(pos[hi - 1])} are not "
+                             "sorted: the index does not describe this file")
+        if lo and hi > lo:
+            self.codes[self.carry:self.carry + hi - lo].copy_(self.codes[self.carry + lo:self.carry + hi].clone())
+        if hi > lo:
+            self.kept.append((hi - lo, line_off[lo:hi].clone(), self.text_base))
+        return p[lo:hi], f[lo:hi], hi - lo
+
+    def _region_error(self, r, pos, flags) -> ValueError:
+        """The file line of a region's record is not known without a full scan: POS and the virtual offset."""
+        from . import tbi
+        for k, off, base in self.kept:
+            if r < k:
+                t = base + int(off[r].item())
+                break
+            r -= k
+        offs, sizes = zip(*self.members)
+        v = int(tbi.virtual_offsets([t], offs, sizes, offs[-1] + 1)[0])
+        what = "; ".join(t for bit, t in FLAG_TEXT.items() if flags & bit)
+        return ValueError(f"{self.name}: record at POS {pos} (virtual offset {v}: byte {v & 0xffff} of the member at "
+                          f"file byte {v >> 16}): {what}")
 
     def finish(self) -> "VcfGenotypes":
         import torch
@@ -305,6 +354,8 @@ class _ChunkParser:
             r = int(bad[0])
             if int(flags[r]) & FLAG_OFFSET:
                 raise RuntimeError(f"{name}: record {r}: the line index gave an offset outside its chunk")
+            if self.region is not None:
+                raise self._region_error(r, int(pos[r]), int(flags[r]) & FLAG_ERRORS)
             raise flag_error(name, _record_line(self.path, r), int(flags[r]) & FLAG_ERRORS)
         seen = int(np.bitwise_or.reduce(flags >> np.uint32(8))) if flags.size else 0
         return VcfGenotypes(self.samples, pos.astype(np.int32, copy=False), alt_bits, miss_bits, self.n_records,
@@ -312,12 +363,21 @@ class _ChunkParser:
 
 
 def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general: bool = False,
-             inflate: str = None) -> VcfGenotypes:
+             inflate: str = None, region=None) -> VcfGenotypes:
     """POS and GT of the VCF at ``path``, the body parsed on ``device``.  ``.gz`` / BGZF is inflated on the host
     (streaming), or with ``inflate="device"`` (``None``: ``DEFAULT_INFLATE``) on the GPU when the file is BGZF.
     ``force_general`` sends every line through the general parse path (same result).  ``ValueError``: what
     ``parse_vcf_host`` raises for the file, a line longer than ``chunk_bytes``, or a BGZF block that does not
-    inflate (``inflate="device"``: "<path>: BGZF block at byte <file offset>: <what>")."""
+    inflate (``inflate="device"``: "<path>: BGZF block at byte <file offset>: <what>").
+
+    ``region=(name, first, last)``: what the whole-file read gives, restricted to the records of sequence ``name``
+    with ``first <= POS <= last`` (1-based, inclusive; by POS, not by overlap: REF is not parsed).  Needs a BGZF
+    file and its tabix index ``path + ".tbi"`` (``ValueError`` without either; ``.csi`` is not read); only the
+    members the index names for the region are read from disk, inflated (zlib member by member, or the device
+    table path) and parsed.  A name the index does not hold, or an empty span, gives an empty result.  An error
+    message of a region read names the record's POS and virtual offset in place of the file line.  The record
+    flags are checked for the region's records only; a line of the span that is shorter than any record raises
+    whether or not it lies in the region (it is met before POS is known), without the file line."""
     import torch
     from .. import native as N
     N.require_gpu()
@@ -327,6 +387,9 @@ def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general
     if mode not in INFLATE_MODES:
         raise ValueError(f"inflate must be one of {INFLATE_MODES}, not {mode!r}")
     name, dev = str(path), torch.device(device)
+    READ_STATS["members_inflated"] = 0
+    if region is not None:
+        return _read_vcf_region(path, name, dev, chunk_bytes, force_general, mode, region)
     if mode == "device":
         from .bgzf import is_bgzf
         if is_bgzf(path):
@@ -345,47 +408,55 @@ def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general
                 raise ValueError(f"{name}: a record in front of the #CHROM header")
         if samples is None:
             raise ValueError(f"{name}: no #CHROM header")
-        cap = (chunk_bytes + 15) // 16 * 16
-        with torch.cuda.device(dev):
-            main, side = torch.cuda.current_stream(), torch.cuda.Stream()
-            pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
-            text = [torch.empty(cap, device=dev, dtype=torch.uint8) for _ in range(2)]
-            uploaded = [torch.cuda.Event(), torch.cuda.Event()]
-            parsed = [torch.cuda.Event(), torch.cuda.Event()]
-            parser = _ChunkParser(path, name, dev, samples, chunk_bytes, force_general)
-            tail, eof, c = b"", False, 0
-            while not eof or tail:
-                b = c & 1
-                buf = pinned[b].numpy()                      # chunk c - 2 left it: its parse was waited for below
-                n = len(tail)
-                buf[:n] = np.frombuffer(tail, np.uint8)
-                view = memoryview(buf)
-                while n < chunk_bytes:
-                    got = fh.readinto(view[n:chunk_bytes])
-                    if not got:
-                        eof = True
-                        break
-                    n += got
-                if eof and n and buf[n - 1] != 10 and n < chunk_bytes:
-                    buf[n] = 10                                # a last line without its newline
-                    n += 1
-                cut = _last_newline(buf, n) + 1
-                if cut == 0 and n:
-                    raise ValueError(f"{name}: a line is longer than chunk_bytes = {chunk_bytes}")
-                tail = buf[cut:n].tobytes()
-                c += 1
-                if cut == 0:
-                    continue
-                padded = (cut + 15) // 16 * 16
-                buf[cut:padded] = 10
-                side.wait_event(parsed[b])                     # text[b] was last read by chunk c - 2's parse
-                with torch.cuda.stream(side):
-                    text[b][:padded].copy_(pinned[b][:padded], non_blocking=True)
-                    uploaded[b].record(side)
-                main.wait_event(uploaded[b])
-                parser.chunk(text[b], cut, eof and not tail, parsed[b], main)
-            main.wait_stream(side)
-            return parser.finish()
+        return _parse_text(fh, _ChunkParser(path, name, dev, samples, chunk_bytes, force_general), chunk_bytes)
+
+
+def _parse_text(fh, parser, chunk_bytes) -> VcfGenotypes:
+    """The body text that ``fh.readinto`` gives, streamed through ``parser`` in chunks of whole lines."""
+    import torch
+    name, dev = parser.name, parser.dev
+    cap = (chunk_bytes + 15) // 16 * 16
+    with torch.cuda.device(dev):
+        main, side = torch.cuda.current_stream(), torch.cuda.Stream()
+        pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        text = [torch.empty(cap, device=dev, dtype=torch.uint8) for _ in range(2)]
+        uploaded = [torch.cuda.Event(), torch.cuda.Event()]
+        parsed = [torch.cuda.Event(), torch.cuda.Event()]
+        tail, eof, c, taken = b"", False, 0, 0
+        while not eof or tail:
+            b = c & 1
+            buf = pinned[b].numpy()                      # chunk c - 2 left it: its parse was waited for below
+            n = len(tail)
+            buf[:n] = np.frombuffer(tail, np.uint8)
+            view = memoryview(buf)
+            parser.text_base = taken - n                 # of buf[0] in the text read so far
+            while n < chunk_bytes:
+                got = fh.readinto(view[n:chunk_bytes])
+                if not got:
+                    eof = True
+                    break
+                n += got
+                taken += got
+            if eof and n and buf[n - 1] != 10 and n < chunk_bytes:
+                buf[n] = 10                                # a last line without its newline
+                n += 1
+            cut = _last_newline(buf, n) + 1
+            if cut == 0 and n:
+                raise ValueError(f"{name}: a line is longer than chunk_bytes = {chunk_bytes}")
+            tail = buf[cut:n].tobytes()
+            c += 1
+            if cut == 0:
+                continue
+            padded = (cut + 15) // 16 * 16
+            buf[cut:padded] = 10
+            side.wait_event(parsed[b])                     # text[b] was last read by chunk c - 2's parse
+            with torch.cuda.stream(side):
+                text[b][:padded].copy_(pinned[b][:padded], non_blocking=True)
+                uploaded[b].record(side)
+            main.wait_event(uploaded[b])
+            parser.chunk(text[b], cut, eof and not tail, parsed[b], main)
+        main.wait_stream(side)
+        return parser.finish()
 
 
 def _bgzf_error(name: str, file_off: int, what: str) -> ValueError:
@@ -420,6 +491,7 @@ def _bgzf_header(path, name, fh):
             if not ok:
                 st = bgzf.inflate_member_host(payload, blk.isize, blk.crc)[1]
                 raise _bgzf_error(name, blk.file_off, bgzf.STATUS_TEXT.get(st, "does not inflate"))
+            READ_STATS["members_inflated"] += 1
             starts.append((blk.file_off, len(head), o + blk.payload_len + 8 - (blk.file_off - pos)))
             head += data
             while True:                                        # whole lines of the header so far
@@ -448,8 +520,131 @@ def _bgzf_header(path, name, fh):
             raise ValueError(f"{name}: no #CHROM header")
 
 
-def _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general) -> VcfGenotypes:
-    """``read_vcf`` of a BGZF file with the blocks inflated on the device.  Per chunk: raw bytes are read into
+class _RawSpan:
+    """The raw bytes [start, end) of an open file, as the reads of the device inflate take them."""
+
+    def __init__(self, fh, start: int, end: int):
+        self.fh, self.left = fh, end - start
+        fh.seek(start)
+
+    def readinto(self, view) -> int:
+        got = self.fh.readinto(view[:min(len(view), self.left)]) if self.left > 0 else 0
+        self.left -= got or 0
+        return got or 0
+
+    def read(self, n: int) -> bytes:
+        data = self.fh.read(max(min(n, self.left), 0))
+        self.left -= len(data)
+        return data
+
+
+class _SpanText:
+    """The text of the members of a span, inflated with zlib member by member (a region read with
+    ``inflate="host"``), as ``readinto`` gives it: ``skip`` bytes of the first member are replaced by '\n', and
+    the member at file offset ``cut_off`` is cut (filled with '\n') from its byte ``cut``."""
+
+    def __init__(self, raw: _RawSpan, name, start, skip, cut_off, cut, parser):
+        self.raw, self.name, self.pos, self.parser = raw, name, start, parser
+        self.skip, self.cut_off, self.cut = skip, cut_off, cut
+        self.rest, self.text, self.at = b"", b"", 0
+
+    def _more(self) -> bool:
+        import zlib
+        from . import bgzf
+        piece = self.raw.read(RAW_PIECE)
+        data = self.rest + piece
+        try:
+            blocks, used = bgzf.bgzf_blocks(data, self.pos)
+        except ValueError as e:
+            raise ValueError(f"{self.name}: {e}") from None
+        if not piece:
+            if data:
+                raise _bgzf_error(self.name, self.pos, "truncated")
+            return False
+        parts = []
+        for blk in blocks:
+            payload = data[blk.payload_off:blk.payload_off + blk.payload_len]
+            try:
+                text = zlib.decompress(payload, -15)
+                ok = len(text) == blk.isize and zlib.crc32(text) == blk.crc
+            except zlib.error:
+                ok = False
+            if not ok:
+                st = bgzf.inflate_member_host(payload, blk.isize, blk.crc)[1]
+                raise _bgzf_error(self.name, blk.file_off, bgzf.STATUS_TEXT.get(st, "does not inflate"))
+            if self.skip:
+                text, self.skip = b"\n" * self.skip + text[self.skip:], 0
+            if self.cut and blk.file_off == self.cut_off:
+                text = text[:self.cut] + b"\n" * (len(text) - self.cut)
+            parts.append(text)
+            self.parser.members.append((blk.file_off, blk.isize))
+            READ_STATS["members_inflated"] += 1
+        self.rest, self.pos = data[used:], self.pos + used
+        self.text, self.at = b"".join(parts), 0
+        return True
+
+    def readinto(self, view) -> int:
+        while self.at == len(self.text):
+            if not self._more():
+                return 0
+        n = min(len(view), len(self.text) - self.at)
+        view[:n] = self.text[self.at:self.at + n]
+        self.at += n
+        return n
+
+
+def _read_vcf_region(path, name, dev, chunk_bytes, force_general, mode, region) -> VcfGenotypes:
+    """``read_vcf(region=...)``: the header from the front of the file, the body from the one span of virtual
+    offsets ``tbi.query`` gives for the region.  Raw bytes are read from the member at ``v_lo >> 16`` to the end
+    of the member at ``v_hi >> 16`` (its length from its own header; not read when ``v_hi & 0xffff`` is 0); the
+    text in front of ``v_lo & 0xffff`` in the first member becomes '\n' (the grammar skips empty lines) and the
+    last member is cut at ``v_hi & 0xffff``."""
+    from . import bgzf, tbi
+    seq, first, last = str(region[0]), int(region[1]), int(region[2])
+    if not bgzf.is_bgzf(path):
+        raise ValueError(f"{name}: a region read needs a BGZF file (bgzip / --vcf_bgzf) and its .tbi index")
+    if not os.path.exists(name + ".tbi"):
+        raise ValueError(f"{name}: a region read needs the tabix index {name}.tbi (write_vcf(index=True) / "
+                         "--vcf_index, or tabix -p vcf); .csi indexes are not read")
+    index = tbi.read(name + ".tbi")
+    with open(path, "rb") as fh:
+        samples, _, _ = _bgzf_header(path, name, fh)
+        span = tbi.query(index, seq, first - 1, last) if first <= last else None
+        if span is None:
+            return _ChunkParser(path, name, dev, samples, 64, force_general).finish()
+        (start, cut_off), (skip, cut) = (v >> 16 for v in span), (v & 0xffff for v in span)
+        end = cut_off
+        if cut:                                            # the last member's length, from its own header
+            fh.seek(cut_off)
+            try:
+                blocks, _ = bgzf.bgzf_blocks(fh.read(bgzf.MAX_BLOCK), cut_off)
+            except ValueError as e:
+                raise ValueError(f"{name}: {e} (does {name}.tbi describe this file?)") from None
+            if not blocks:
+                raise _bgzf_error(name, cut_off, f"truncated (does {name}.tbi describe this file?)")
+            end = cut_off + blocks[0].payload_off + blocks[0].payload_len + 8
+        raw = _RawSpan(fh, start, end)
+        if end - start <= SMALL_SPAN:                      # buffers of the span's size, not of chunk_bytes
+            data = raw.read(end - start)
+            try:
+                blocks, used = bgzf.bgzf_blocks(data, start)
+            except ValueError as e:
+                raise ValueError(f"{name}: {e} (does {name}.tbi describe this file?)") from None
+            if used != end - start:
+                raise _bgzf_error(name, start + used, f"truncated (does {name}.tbi describe this file?)")
+            chunk_bytes = min(chunk_bytes, max(64, sum(blk.isize for blk in blocks) + 64))
+            raw = _RawSpan(io.BytesIO(data), 0, len(data))
+        parser = _ChunkParser(path, name, dev, samples, chunk_bytes, force_general, region=(seq, first, last))
+        if mode == "device":
+            return _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general, parser,
+                                            (raw, start, end, skip, cut_off, cut))
+        return _parse_text(_SpanText(raw, name, start, skip, cut_off, cut, parser), parser, chunk_bytes)
+
+
+def _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general, parser=None, span=None) -> VcfGenotypes:
+    """``read_vcf`` of a BGZF file with the blocks inflated on the device (``span``: of a region read, the raw
+    bytes, their file range, and where the text begins in the first member and ends in the last).  Per chunk:
+    raw bytes are read into
     one of two pinned buffers RAW_PIECE at a time and their block headers walked until the next block would not
     fit (``tail + sum ISIZE <= chunk_bytes``, at most MAX_CHUNK_BLOCKS blocks, the raw buffer); the taken bytes
     go up on the side stream; the blocks are inflated into ``text[b]`` behind the previous chunk's tail; status
@@ -458,11 +653,16 @@ def _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general) -> Vcf
     import torch
     from .. import kernels as K
     from . import bgzf
-    with open(path, "rb") as fh:
-        samples, off0, skip = _bgzf_header(path, name, fh)
-        fh.seek(off0)
+    with (open(path, "rb") if span is None else contextlib.nullcontext(span[0])) as fh:
+        span_cut_off = span_cut = 0                    # a region's end: the member it lies in, the text byte in it
+        if span is None:
+            samples, off0, skip = _bgzf_header(path, name, fh)
+            fh.seek(off0)
+            end = os.path.getsize(path)
+        else:
+            _, off0, end, skip, span_cut_off, span_cut = span
         cap = (chunk_bytes + 15) // 16 * 16
-        rawcap = min(chunk_bytes // 4 + 2 * RAW_PIECE, max(os.path.getsize(path) - off0, 0) + 64)
+        rawcap = min(chunk_bytes // 4 + 2 * RAW_PIECE, max(end - off0, 0) + 64)
         with torch.cuda.device(dev):
             main, side = torch.cuda.current_stream(), torch.cuda.Stream()
             raw = [torch.empty(rawcap, dtype=torch.uint8).pin_memory() for _ in range(2)]
@@ -473,10 +673,11 @@ def _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general) -> Vcf
             res = torch.empty(2 + MAX_CHUNK_BLOCKS, device=dev, dtype=torch.int32)     # last newline (i64), status
             uploaded = [torch.cuda.Event(), torch.cuda.Event()]
             parsed = [torch.cuda.Event(), torch.cuda.Event()]
-            parser = _ChunkParser(path, name, dev, samples, chunk_bytes, force_general)
+            if parser is None:
+                parser = _ChunkParser(path, name, dev, samples, chunk_bytes, force_general)
             rest = np.zeros(0, np.uint8)           # raw bytes read and not yet taken: whole blocks and a partial one
             base = off0                            # file offset of rest[0]
-            tail_len, eof, c = 0, False, 0
+            tail_len, eof, c, text_seen = 0, False, 0, 0
             deferred = None                        # a record-level error: raised once every block has inflated
             while not eof or tail_len or rest.size:
                 b = c & 1
@@ -529,9 +730,15 @@ def _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general) -> Vcf
                         uploaded[b].record(side)
                     main.wait_event(uploaded[b])
                     K.bgzf_inflate(comp[b][:o], table, text[b], res[2:], table_dev)
+                    READ_STATS["members_inflated"] += nb
                     if skip:                                   # the header lines in front of the body in its first block
                         text[b][:skip].fill_(10)
                         skip = 0
+                    if span_cut and taken[-1][0] == span_cut_off:   # a region's last member: the text behind the span
+                        text[b][taken[-1][3] + span_cut:taken[-1][3] + taken[-1][4]].fill_(10)
+                    if parser.region is not None:
+                        parser.members += [(t[0], t[4]) for t in taken]
+                parser.text_base, text_seen = text_seen - tail_len, text_seen + n_text - tail_len
                 if last and n_text < chunk_bytes:
                     text[b][n_text:n_text + 1].fill_(10)       # a last line without its newline
                     n_text += 1

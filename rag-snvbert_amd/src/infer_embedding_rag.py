@@ -66,12 +66,19 @@ def parse_args(argv=None):
     p.add_argument("--vcf_bgzf", action="store_true",
                    help="write imputed.vcf.gz (bgzipped: BGZF members and the EOF block) instead of imputed.vcf; with "
                         "--vcf_writer host through zlib, with --vcf_writer device deflated on the GPU (csrc/deflate.hip)")
+    p.add_argument("--vcf_index", action="store_true",
+                   help="with --vcf_bgzf: also write imputed.vcf.gz.tbi, the tabix index of the file (dataset/tbi.py), "
+                        "from the offsets the writer already knows: no second pass over the file")
     p.add_argument("--vcf_info", action="store_true",
                    help="write AF, DR2, R2 and the IMP flag into the INFO column of imputed.vcf (per-site sums on the "
                         "GPU, csrc/quality.hip; quality.py); off: INFO stays '.'")
     p.add_argument("--truth_vcf", type=str, default=None,
                    help="a .vcf / .vcf.gz with the true genotypes: the imputed sites it holds are scored against it "
                         "(dosage r2, concordance, non-reference concordance by MAF bin) into quality.npz and accuracy.tsv")
+    p.add_argument("--truth_region", default="all", choices=["all", "imputed"],
+                   help="all: read the whole --truth_vcf; imputed: read only --chrom over the span of the imputed "
+                        "positions, through the file's .tbi index (BGZF only).  The same scores either way; "
+                        "quality.npz's truth_row counts from the first record read")
     p.add_argument("--maf_bins", type=str, default=None,
                    help="MAF bin edges of accuracy.tsv, comma separated (default 0,0.001,0.005,0.01,0.05,0.1,0.2,0.5)")
     p.add_argument("--panel_codes", default="u8", choices=["u8", "bits"],
@@ -88,7 +95,10 @@ def parse_args(argv=None):
     p.add_argument("--vcf_inflate", default="host", choices=["host", "device"],
                    help="where BGZF .vcf.gz inputs are inflated: host (zlib) or device (csrc/inflate.hip, one wave "
                         "per block); the same arrays either way, files that are not BGZF stay on the host")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.vcf_index and not args.vcf_bgzf:
+        p.error("--vcf_index needs --vcf_bgzf: a .tbi indexes a bgzipped file")
+    return args
 
 
 def postprocess(probs_h1: torch.Tensor, probs_h2: torch.Tensor):
@@ -138,6 +148,9 @@ class _BgzfText:
         self.fh.write(s.encode(self.encoding))
         return len(s)
 
+    def tell_virtual(self) -> int:
+        return self.fh.tell_virtual()
+
     def __enter__(self):
         return self
 
@@ -145,15 +158,25 @@ class _BgzfText:
         self.fh.close()
 
 
-def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, bgzf=False, info=None):
+def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, bgzf=False, info=None,
+              index=False):
     """VCF 4.2 records of the imputed sites (utils.py:378-479 layout: FORMAT GT:HDS:GP:DS,
     ID '.', REF/ALT '.' unless given, QUAL 0, FILTER PASS).  ``pos_flag`` selects the sites
     written (the reference writes only flagged = imputed positions, infer_embedding_rag.py:237).
     ``bgzf``: the same text as a bgzipped file (BGZF members of 0xff00 bytes, zlib level 6, the EOF block).
     ``info``: one INFO string per site row (``quality.info_strings``: AF, DR2, R2, IMP) in place of '.', and the
-    four ##INFO header lines that declare them."""
+    four ##INFO header lines that declare them.
+    ``index`` (needs ``bgzf``): also write the tabix index ``path + ".tbi"`` (dataset/tbi.py) from the virtual
+    offsets the BGZF writer reports around every record: no second pass over the file, and no byte of the file
+    itself changes.  A position >= 2^29 raises ``ValueError`` before anything is written."""
     if info is not None and len(info) != len(pos):
         raise ValueError("info must hold one string per site row")
+    if index:
+        if not bgzf:
+            raise ValueError("index=True needs bgzf=True: a .tbi indexes a bgzipped file")
+        from .dataset import tbi
+        beg, end = tbi.vcf_intervals(pos, pos_flag, ref)
+        voff = []
     with (_BgzfText(path) if bgzf else open(path, "w")) as f:
         f.write("##fileformat=VCFv4.2\n##source=rag-snvbert_amd\n")
         if info is not None:
@@ -170,8 +193,14 @@ def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, al
             r = ref[i] if ref is not None else "."
             a = alt[i] if alt is not None else "."
             inf = info[i] if info is not None else "."
+            if index:
+                voff.append(f.tell_virtual())
             f.write(f"{chrom}\t{int(pos[i])}\t.\t{r}\t{a}\t0.0\tPASS\t{inf}\tGT:HDS:GP:DS\t" +
                     "\t".join(vcf_cells(h1[i], h2[i], gt[i])) + "\n")
+    if index:
+        voff.append(f.tell_virtual())                      # closed: the EOF block's offset
+        n = len(voff) - 1
+        tbi.build([str(chrom)] if n else [], np.zeros(n, np.int64), beg, end, voff[:-1], voff[1:]).write(str(path) + ".tbi")
 
 
 from .vcf_device import milli_f32, write_vcf_device  # noqa: E402  (the opt-in device writer of the same file)
@@ -334,7 +363,11 @@ def site_quality(args, ds, dev, src, flag):
     truth = row = col = None
     if args.truth_vcf:
         from .dataset.vcf_reader import read_vcf
-        tv = read_vcf(args.truth_vcf, dev)
+        region = None
+        if args.truth_region == "imputed":               # through the .tbi: only the members that span touches
+            imputed = ori_pos[np.asarray(flag, bool)]
+            region = (args.chrom, int(imputed.min()), int(imputed.max())) if imputed.size else (args.chrom, 1, 0)
+        tv = read_vcf(args.truth_vcf, dev, region=region)
         vg = getattr(ds, "vcf_genotypes", None)
         row, col = Q.truth_maps(tv, ori_pos, None if vg is None else list(vg.samples), n_samples=S)
         row = np.where(flag, row, -1).astype(np.int32)
@@ -422,11 +455,11 @@ def infer(argv=None):
             # (several ranks: the gathered ones) uploaded chunk by chunk
             src = site_dev if site_dev is not None else dict(h1=h1, h2=h2, gt=gt)
             write_vcf_device(vcf_path, args.chrom, ds.ori_pos, src["h1"], src["h2"], src["gt"], samples,
-                             pos_flag=flag, device=dev, bgzf=args.vcf_bgzf, info=info)
+                             pos_flag=flag, device=dev, bgzf=args.vcf_bgzf, info=info, index=args.vcf_index)
             src = None
         else:
             write_vcf(vcf_path, args.chrom, ds.ori_pos, h1, h2, gt, samples, pos_flag=flag, bgzf=args.vcf_bgzf,
-                      info=info)
+                      info=info, index=args.vcf_index)
     site_dev = None                    # the device result arrays are freed after the last reader
     print(f"imputed {len(ds)} sample-windows in {res['seconds']:.2f}s "
           f"({res['masked_snvs'] / res['seconds']:.0f} masked SNVs/s)", flush=True)

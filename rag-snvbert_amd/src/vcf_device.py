@@ -11,6 +11,9 @@ The fixed width holds for values in [0, 9.9995) only.  The kernel counts every o
 infinity, a set sign bit, >= 9.9995); the count is read once per chunk before that chunk's bytes reach
 the file, and a nonzero count discards the partial file and lets ``write_vcf`` write the whole of it.
 
+``bgzf=True`` deflates each chunk into BGZF members on the device (csrc/deflate.hip); ``index=True`` also writes
+the file's tabix index from the line offsets and the member lengths, without reading the file back.
+
 ``milli_f32`` restates the kernel's integer '%.3f' rounding in numpy (checked against Python's own
 formatting without a GPU).
 """
@@ -116,7 +119,7 @@ def _host(a):
 
 
 def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, device=None,
-                     chunk_bytes: int = DEFAULT_CHUNK_BYTES, bgzf: bool = False, info=None) -> bool:
+                     chunk_bytes: int = DEFAULT_CHUNK_BYTES, bgzf: bool = False, info=None, index: bool = False) -> bool:
     """``write_vcf`` with the records formatted on ``device``: the same file, byte for byte.
 
     ``bgzf``: the file is bgzipped.  Each chunk's text is deflated into BGZF members of 0xff00 bytes and packed
@@ -127,6 +130,12 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
 
     ``info``: one INFO string per site row, as ``write_vcf(info=...)``: it takes the place of '.' in the line
     prefixes (host-built, of any width) and adds the four ##INFO header lines.
+
+    ``index`` (needs ``bgzf``): also write the tabix index ``path + ".tbi"`` (dataset/tbi.py) without reading the
+    file back.  The byte offset of every line in its chunk's text is known on the host; each chunk's member lengths
+    (4 bytes per 0xff00 bytes of text) cross with its packed bytes, on the same stream and event, and a prefix sum
+    over them turns the line offsets into virtual offsets.  A position >= 2^29 raises ``ValueError`` before
+    anything is written; the fallback below removes the partial file and the host writer writes both files.
 
     h1 / h2 [n, S] and gt [n, S, 4] are float32 numpy arrays, host tensors or device tensors.  Device
     tensors are formatted in place; host arrays are uploaded one chunk of selected rows at a time.
@@ -152,6 +161,11 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     if info is not None and len(info) != n:
         raise ValueError("info must hold one string per site row")
     flag = None if pos_flag is None else _host(pos_flag)
+    if index:
+        if not bgzf:
+            raise ValueError("index=True needs bgzf=True: a .tbi indexes a bgzipped file")
+        from .dataset import tbi
+        beg, end = tbi.vcf_intervals(pos, flag, ref)
     rows, blob, prefix_off = site_prefixes(chrom, pos, flag, ref, alt, info=info)
     length = line_lengths(prefix_off, S)
     chunks = plan_chunks(length, chunk_bytes)
@@ -164,6 +178,8 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
         with open(path, "w") as f:
             f.write(header_lines(samples, info is not None))
     if not chunks:
+        if index:
+            tbi.build([], [], [], [], [], []).write(str(path) + ".tbi")
         return True
 
     cap = max(int(length[lo:hi].sum()) for lo, hi in chunks)
@@ -184,6 +200,9 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
             small = torch.zeros(2, 4, device=dev, dtype=torch.int32)     # per buffer: bad count, -, total (i64)
             small_host = torch.zeros(2, 4, dtype=torch.int32).pin_memory()
             counted, totals = [torch.cuda.Event(), torch.cuda.Event()], [0, 0]
+        if index:
+            mlen_host = [torch.zeros(slots, dtype=torch.int32).pin_memory() for _ in range(2)]
+            file_off, v_beg = [os.path.getsize(path)], []     # of the next chunk's first member; per chunk, of its lines
         ok = True
         with open(path, "ab") as f:
 
@@ -193,6 +212,15 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
                 copied[b].synchronize()
                 if bgzf:                               # start_copy saw its count
                     f.write(memoryview(pinned[b].numpy())[:totals[b]])
+                    if index:
+                        lo, hi = chunks[c]
+                        text_off = np.concatenate([[0], np.cumsum(length[lo:hi])])
+                        nm = -(-int(text_off[-1]) // BGZF_BLOCK)
+                        mlen = mlen_host[b].numpy()[:nm].astype(np.int64)
+                        assert int(mlen.sum()) == totals[b], "the member lengths of a chunk do not add up to its bytes"
+                        member_off = file_off[0] + np.cumsum(mlen) - mlen
+                        v_beg.append(member_off[text_off[:-1] // BGZF_BLOCK] << 16 | text_off[:-1] % BGZF_BLOCK)
+                        file_off[0] += totals[b]
                     return True
                 if int(bad_host[b]) != 0:
                     return False
@@ -210,6 +238,10 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
                 assert 0 <= totals[b] <= packed[b].numel(), "the members of a chunk exceed their bound"
                 with torch.cuda.stream(side):
                     pinned[b][:totals[b]].copy_(packed[b][:totals[b]], non_blocking=True)
+                    if index:
+                        lo, hi = chunks[c]
+                        nm = -(-int(length[lo:hi].sum()) // BGZF_BLOCK)
+                        mlen_host[b][:nm].copy_(member_len[b][:nm], non_blocking=True)
                     copied[b].record(side)
                 return True
 
@@ -255,10 +287,13 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
         main.wait_stream(side)                         # the buffers go back to the allocator behind the copies
         torch.cuda.synchronize(dev)
     if ok:
+        if index:                                      # a line ends where the next begins; the last at the EOF block
+            v = np.concatenate(v_beg + [[file_off[0] << 16]]).astype(np.uint64)
+            tbi.build([str(chrom)], np.zeros(v.size - 1, np.int64), beg, end, v[:-1], v[1:]).write(str(path) + ".tbi")
         return True
     os.remove(path)
     print("write_vcf_device: a value does not fit the fixed-width cell (NaN, infinite, negative or >= 9.9995); "
           "the host writer writes the file", flush=True)
     write_vcf(path, chrom, pos, _host(h1), _host(h2), _host(gt), samples, pos_flag=flag, ref=ref, alt=alt, bgzf=bgzf,
-              info=info)
+              info=info, index=index)
     return False

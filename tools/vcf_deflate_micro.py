@@ -5,7 +5,9 @@
 Two sets of values: tools/vcf_micro.py's random probabilities (the worst case for compression) and mostly
 confident calls (0.9 of the cells hold 0 / 1 probabilities).  Per set, for the complete file written to a local
 temporary directory: the host ``write_vcf(bgzf=True)`` (zlib level 6 through BgzfWriter), ``write_vcf_device``
-plain and ``write_vcf_device(bgzf=True)``, both from device arrays; the file sizes; the deflate and the pack
+plain, ``write_vcf_device(bgzf=True)`` and ``write_vcf_device(bgzf=True, index=True)`` (the last two alternate,
+so that the cost of the tabix index shows against the same process's spread), all from device arrays; the file
+sizes and the ``.tbi``'s; the deflate and the pack
 kernels alone (device events around the launches of one chunk's members, no copy); and the device file's size
 over zlib level 1 and level 6 at the same member size, on the first 64 members of the text.
 
@@ -88,14 +90,20 @@ def main():
             t_host = time.perf_counter() - t0
             print(f"host write_vcf(bgzf=True)        complete file {t_host:9.3f} s  "
                   f"{os.path.getsize(os.path.join(tmp, 'host.vcf.gz'))} bytes (zlib level 6)", flush=True)
-            for label, name, bg in (("device writer, plain", "dev.vcf", False), ("device writer, bgzf=True", "dev.vcf.gz", True)):
-                ts = []
-                for _ in range(3):
+            arms = (("device writer, plain", "dev.vcf", False, False), ("device writer, bgzf=True", "dev.vcf.gz", True, False),
+                    ("device writer, bgzf + index", "dev.vcf.gz", True, True))
+            ts = {arm[0]: [] for arm in arms}
+            for _ in range(3):                                          # the arms alternate
+                for label, name, bg, ix in arms:
                     t0 = time.perf_counter()
-                    assert write_vcf_device(os.path.join(tmp, name), "21", pos, d1, d2, dg, samples, device=DEV, bgzf=bg)
-                    ts.append(time.perf_counter() - t0)
-                print(f"{label:32s} complete file {min(ts):9.3f} s  {os.path.getsize(os.path.join(tmp, name))} bytes  "
-                      f"(3 runs: {' '.join(f'{t:.3f}' for t in ts)})", flush=True)
+                    assert write_vcf_device(os.path.join(tmp, name), "21", pos, d1, d2, dg, samples, device=DEV, bgzf=bg,
+                                            index=ix)
+                    ts[label].append(time.perf_counter() - t0)
+            for label, name, bg, ix in arms:
+                print(f"{label:32s} complete file {min(ts[label]):9.3f} s  {os.path.getsize(os.path.join(tmp, name))} bytes  "
+                      f"(3 runs: {' '.join(f'{t:.3f}' for t in ts[label])})", flush=True)
+            print(f"{'':32s} dev.vcf.gz.tbi {os.path.getsize(os.path.join(tmp, 'dev.vcf.gz.tbi'))} bytes for {n} records",
+                  flush=True)
             with open(os.path.join(tmp, "dev.vcf"), "rb") as f:
                 plain = f.read()
             with open(os.path.join(tmp, "dev.vcf.gz"), "rb") as f:
@@ -112,7 +120,7 @@ def main():
             z = {lv: sum(len(B.bgzf_member(part[o:o + 0xff00], lv)) for o in range(0, len(part), 0xff00)) for lv in (1, 6)}
             print(f"first {len(part)} bytes of text: device {dev}, zlib level 1 {z[1]} (device / zlib = {dev / z[1]:.3f}), "
                   f"zlib level 6 {z[6]} (device / zlib = {dev / z[6]:.3f})", flush=True)
-            for name in ("host.vcf.gz", "dev.vcf", "dev.vcf.gz"):
+            for name in ("host.vcf.gz", "dev.vcf", "dev.vcf.gz", "dev.vcf.gz.tbi"):
                 os.remove(os.path.join(tmp, name))
             del d1, d2, dg
 
