@@ -824,6 +824,27 @@ int snvrag_panel_gather_bits(const uint8_t* bits, int64_t N, int64_t ld_bits, in
 int snvrag_vcf_unpack_gt(const uint8_t* alt_bits, const uint8_t* miss_bits, int64_t ld_bits, int64_t S,
                          int64_t n_sites, int8_t* gt, void* stream);
 
+/* Genotype counts of a panel per site and population, from the reader's bit rows (csrc/panel_stats.hip; what
+ * prepare_data_v4_0411.py:116-231 takes from four per-population CSVs; src/dataset/panel_stats.py
+ * panel_counts_host is the specification, freq_from_counts turns the counts into Freq.npy).
+ *   alt_bits, miss_bits  u8 [2 S][ld_bits], the snvrag_vcf_pack_rows layout: haplotype h of sample s in row
+ *          2 s + h, site r at bit r & 7 of byte r >> 3.  Any ld_bits >= ceil(n_sites / 8) and any byte alignment
+ *          of the rows; bytes past ceil(n_sites / 8) and the bits of the last byte past n_sites may hold anything
+ *          and are not counted; no load leaves [row, row + ceil(n_sites / 8)) of a row.  An ALT bit under a set
+ *          missing bit is ignored.
+ *   order  i32 [S]: sample numbers sorted by population (stable);  pop_start i32 [P + 1]: population p owns
+ *          order[pop_start[p] : pop_start[p + 1]].  An order entry outside [0, S) loads and counts nothing.
+ *   counts i32 [6][5][n_sites], every element written by the launch with a plain store: row p < P is population
+ *          p, rows P .. 4 are zero, row 5 is the sum of the population rows.  The five columns per site:
+ *          n_ref, n_het, n_hom (samples with both alleles called and 0, 1, 2 ALT alleles), n_alt (called alleles
+ *          that are ALT), n_called (called alleles); a haploid or half-missing call adds to the last two only.
+ * Integers throughout: two launches, and any launch geometry, give the same bits.  All pointers are device
+ * pointers.  Refused: a null pointer, S outside [1, 2^29), P outside [1, 5], n_sites outside [0, 2^31),
+ * ld_bits < ceil(n_sites / 8), order / pop_start / counts not 4-byte aligned.  n_sites == 0 launches nothing. */
+int snvrag_panel_counts(const uint8_t* alt_bits, const uint8_t* miss_bits, int64_t ld_bits, int64_t S,
+                        int64_t n_sites, const int32_t* order, const int32_t* pop_start, int64_t P,
+                        int32_t* counts, void* stream);
+
 /* Device inflate of BGZF blocks (csrc/inflate.hip; the gzip layer under allel.read_vcf for a bgzipped
  * .vcf.gz).  The decoder is csrc/inflate_core.h; its specification, status for status, is
  * src/dataset/bgzf.py inflate_block_host.

@@ -252,8 +252,22 @@ class InferDataset(torch.utils.data.Dataset):
         return TrainDataset.to_tensors(self, out)
 
     @classmethod
-    def from_file(cls, vocab, vcfpath, panelpath, freqpath, typepath, poppath, pospath):
-        gt, pos, t2i, p2i, pos2i, vg = _read_inputs_vcf(vcfpath, typepath, poppath, pospath)
-        ds = cls(vocab, gt, pos, PanelData.from_file(panelpath), np.load(freqpath), t2i, p2i, pos2i)
+    def from_file(cls, vocab, vcfpath, panelpath, freqpath, typepath, poppath, pospath, tables=None):
+        """``tables`` (``panel_stats.build_tables``: freq, type_to_idx, pop_to_idx, pos_to_idx in memory) stands in
+        for the four table files, whose paths are then not opened."""
+        if tables is None:
+            gt, pos, t2i, p2i, pos2i, vg = _read_inputs_vcf(vcfpath, typepath, poppath, pospath)
+            freq = np.load(freqpath)
+            panel = PanelData.from_file(panelpath)
+        else:
+            gt, pos, vg = read_genotypes(vcfpath)
+            gt[gt > 0] = 1
+            freq, t2i, p2i, pos2i = (tables[k] for k in ("freq", "type_to_idx", "pop_to_idx", "pos_to_idx"))
+            panel = PanelData.from_file(panelpath)
+            for i, pop in enumerate(panel.pop_list[:gt.shape[1]].tolist()):
+                if pop not in p2i:
+                    raise ValueError(f"{panelpath}: sample {i} is of population {pop!r}, which the reference panel "
+                                     f"does not hold (its populations: {', '.join(k for k in p2i if k != 'Global')})")
+        ds = cls(vocab, gt, pos, panel, freq, t2i, p2i, pos2i)
         ds.vcf_genotypes = vg
         return ds

@@ -159,12 +159,19 @@ class EmbeddingRAGInferDataset(InferDataset):
 
     @classmethod
     def from_file(cls, vocab, vcfpath, panelpath, freqpath, typepath, poppath, pospath, ref_vcf_path=None,
-                  embedding_layer=None, build_ref_data=True, n_gpu=1, name="infer", **kw):
-        base = InferDataset.from_file(vocab, vcfpath, panelpath, freqpath, typepath, poppath, pospath)
+                  embedding_layer=None, build_ref_data=True, n_gpu=1, name="infer", tables=None,
+                  ref_panel_vcf=None, **kw):
+        """``tables``: see ``InferDataset.from_file``.  ``ref_panel_vcf``: the panel's ``VcfGenotypes`` when the
+        caller has read ``ref_vcf_path`` already (the file is then not read again)."""
+        base = InferDataset.from_file(vocab, vcfpath, panelpath, freqpath, typepath, poppath, pospath, tables=tables)
+        if ref_panel_vcf is not None:
+            kw.update(ref_gt=ref_panel_vcf.gt(), ref_pos=ref_panel_vcf.pos)
         ds = cls(vocab, base.vcf, base.pos, base.panel, base.freq, base.type_to_idx, base.pop_to_idx,
                  base.pos_to_idx, ref_vcf_path=ref_vcf_path, embedding_layer=embedding_layer,
                  build_ref_data=build_ref_data, n_gpu=n_gpu, name=name, **kw)
         ds.vcf_genotypes = base.vcf_genotypes
+        if ref_panel_vcf is not None:
+            ds.ref_panel_vcf = ref_panel_vcf
         return ds
 
     @classmethod

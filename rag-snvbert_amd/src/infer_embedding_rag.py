@@ -95,9 +95,22 @@ def parse_args(argv=None):
     p.add_argument("--vcf_inflate", default="host", choices=["host", "device"],
                    help="where BGZF .vcf.gz inputs are inflated: host (zlib) or device (csrc/inflate.hip, one wave "
                         "per block); the same arrays either way, files that are not BGZF stay on the host")
+    p.add_argument("--ref_panel_pops", type=str, default=None,
+                   help="the .panel file of --ref_panel (a .vcf / .vcf.gz): Freq.npy and the pos / pop maps are counted "
+                        "from the panel's genotypes on the GPU (dataset/panel_stats.py) in place of --freq_path, "
+                        "--pop_path, --pos_path and --type_path; nothing is written (build_panel_stats writes them)")
     args = p.parse_args(argv)
     if args.vcf_index and not args.vcf_bgzf:
         p.error("--vcf_index needs --vcf_bgzf: a .tbi indexes a bgzipped file")
+    if args.ref_panel_pops:
+        given = [f"--{n}" for n in ("freq_path", "pop_path", "pos_path", "type_path") if getattr(args, n) is not None]
+        if given:
+            p.error(f"--ref_panel_pops builds the tables from --ref_panel: it does not go with {', '.join(given)}")
+        if args.synthetic:
+            p.error("--ref_panel_pops does not go with --synthetic")
+        from .dataset.vcf_reader import is_vcf_path
+        if not args.ref_panel or not is_vcf_path(args.ref_panel):
+            p.error("--ref_panel_pops needs --ref_panel, a .vcf or .vcf.gz file")
     return args
 
 
@@ -212,10 +225,18 @@ def build_dataset(args):
     if not args.synthetic:
         from .dataset.dataset import PanelData
         vocab = WordVocab(list(PanelData.from_file(args.infer_panel).pop_class_dict.keys()))
+        extra = {}
+        if getattr(args, "ref_panel_pops", None):
+            # the panel VCF is read once: the same bit rows give the tables here and the kNN index later
+            from .dataset import vcf_reader
+            from .dataset.panel_stats import build_tables
+            dev = torch.device("cuda", torch.cuda.current_device())
+            panel_vg = vcf_reader.read_vcf(args.ref_panel, dev)
+            extra = dict(tables=build_tables(panel_vg, args.ref_panel_pops, dev), ref_panel_vcf=panel_vg)
         ds = EmbeddingRAGInferDataset.from_file(vocab, args.infer_dataset, args.infer_panel, args.freq_path,
                                                 args.type_path, args.pop_path, args.pos_path,
                                                 ref_vcf_path=args.ref_panel, window_len=args.window_len,
-                                                index_window_len=args.index_window_len)
+                                                index_window_len=args.index_window_len, **extra)
         ds.set_panel_codes(args.panel_codes)
         return ds, vocab
     from .dataset.synthetic import make_infer_arrays, make_infer_dataset

@@ -914,6 +914,33 @@ def vcf_unpack_gt(alt_bits: torch.Tensor, miss_bits: torch.Tensor, n_sites: int)
     return gt
 
 
+def panel_counts(alt_bits: torch.Tensor, miss_bits: torch.Tensor, n_sites: int, order: torch.Tensor,
+                 pop_start: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Genotype counts i32 [6, 5, n_sites] of the bit rows ``alt_bits`` / ``miss_bits`` u8 [2 S, >= ceil(n_sites / 8)]
+    (``VcfGenotypes`` layout; rows may be views: any row stride that holds the sites, any byte alignment) per
+    population: ``order`` i32 [S] the samples sorted by population, ``pop_start`` i32 [P + 1], 1 <= P <= 5.
+    Row p < P is population p, rows P..4 are zero, row 5 the whole panel; columns n_ref, n_het, n_hom, n_alt,
+    n_called (``dataset/panel_stats.py`` panel_counts_host is the specification).  Every element of the result
+    is written (``out``: a contiguous i32 [6, 5, n_sites] to write into)."""
+    N.require_gpu(alt_bits, miss_bits, order, pop_start)
+    nb = (n_sites + 7) // 8
+    for b in (alt_bits, miss_bits):
+        assert b.dtype == torch.uint8 and b.dim() == 2 and b.shape[0] == alt_bits.shape[0] and b.shape[1] >= nb
+        assert b.shape[1] <= 1 or b.stride(1) == 1
+    S = alt_bits.shape[0] // 2
+    assert alt_bits.shape[0] == 2 * S and S >= 1
+    ld = alt_bits.stride(0) if alt_bits.shape[0] > 1 else max(alt_bits.shape[1], nb)
+    assert all(b.shape[0] <= 1 or b.stride(0) == ld for b in (alt_bits, miss_bits)) and ld >= nb
+    assert order.dtype == pop_start.dtype == torch.int32 and order.is_contiguous() and pop_start.is_contiguous()
+    assert order.numel() == S and pop_start.numel() >= 2
+    if out is None:
+        out = torch.empty(6, 5, n_sites, device=alt_bits.device, dtype=torch.int32)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == (6, 5, n_sites)
+    check(N.lib().snvrag_panel_counts(ptr(alt_bits), ptr(miss_bits), ld, S, n_sites, ptr(order), ptr(pop_start),
+                                      pop_start.numel() - 1, ptr(out), stream_ptr()), "panel_counts")
+    return out
+
+
 def bgzf_table(in_off, out_off, in_len, isize, crc, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The block table of ``bgzf_inflate`` from five sequences: host i64 [n, 4] = in_off, out_off,
     in_len | isize << 32, crc (into the first rows of ``out`` when given, e.g. a pinned buffer)."""
