@@ -824,6 +824,25 @@ int snvrag_panel_gather_bits(const uint8_t* bits, int64_t N, int64_t ld_bits, in
 int snvrag_vcf_unpack_gt(const uint8_t* alt_bits, const uint8_t* miss_bits, int64_t ld_bits, int64_t S,
                          int64_t n_sites, int8_t* gt, void* stream);
 
+/* The CHROM, ID, REF and ALT strings of the same text chunk (opt-in: read_vcf(columns=True); the specification
+ * is src/dataset/vcf_reader.py site_columns_host).  text, nbytes, line_off as above.
+ * snvrag_vcf_cols_span: spans i32 [n_lines][8] = (start, length) of columns 1, 3, 4 and 5 of every line, start
+ *   relative to text.  A column runs from behind the tab in front of it (the line start for CHROM) to the next
+ *   tab or, where the line ends first, to the line's end without the '\r' of a "\r\n".  A column the line does
+ *   not reach is (that line end, 0); a line whose offset lies outside [0, nbytes) gives eight zeros.  A line
+ *   with fewer than nine columns is refused by snvrag_vcf_parse_gt (flag bit 0), so there is no error channel.
+ * snvrag_vcf_cols_gather: item i = c * n_lines + r is column c (0 .. 3) of record r; off i64 [4 n_lines + 1] is
+ *   the exclusive prefix sum of the items' lengths (the caller's), and the item's bytes are copied to
+ *   blob[off[i], off[i + 1]).  An item whose span leaves [0, nbytes), whose length is not off[i + 1] - off[i],
+ *   or whose range leaves [0, blob_bytes) copies nothing; bytes of blob outside the items' ranges are not
+ *   written.  Plain byte stores.
+ * Refused: a null pointer, nbytes outside [1, 2^31), n_lines outside [0, nbytes], text not 16-byte aligned,
+ * line_off / off not 8-byte aligned, spans not 4-byte aligned, blob_bytes < 0.  n_lines == 0 launches nothing. */
+int snvrag_vcf_cols_span(const uint8_t* text, int64_t nbytes, const int64_t* line_off, int64_t n_lines,
+                         int32_t* spans, void* stream);
+int snvrag_vcf_cols_gather(const uint8_t* text, int64_t nbytes, const int32_t* spans, int64_t n_lines,
+                           const int64_t* off, uint8_t* blob, int64_t blob_bytes, void* stream);
+
 /* Genotype counts of a panel per site and population, from the reader's bit rows (csrc/panel_stats.hip; what
  * prepare_data_v4_0411.py:116-231 takes from four per-population CSVs; src/dataset/panel_stats.py
  * panel_counts_host is the specification, freq_from_counts turns the counts into Freq.npy).

@@ -26,6 +26,10 @@
 //                store 8 bytes each in one instruction.
 //   gather bits  a window's PanelIndex rows for an arbitrary site list, straight from the bit rows.
 //   unpack gt    int8 [n, S, 2] (0 / 1, -1 missing) of the bit rows, for VcfGenotypes.gt().
+//   site columns CHROM, ID, REF, ALT (opt-in, read_vcf(columns=True); specification site_columns_host): one wave
+//                per line walks to the fifth tab and writes four (start, length) spans; after an exclusive scan
+//                of the lengths (the caller's) a lane per string copies up to 16 bytes into the packed blob,
+//                and the longer strings of a wave are copied by the whole wave, 64 bytes per step.
 #include "common.h"
 
 namespace snvrag {
@@ -475,6 +479,101 @@ __global__ __launch_bounds__(256) void vcf_unpack_gt_kernel(const uint8_t* __res
   }
 }
 
+// ------------------------------------------------------------------------------------- site columns --
+// CHROM, ID, REF and ALT (columns 1, 3, 4, 5) of every line as (start, length) in the chunk's text: spans
+// i32 [n_lines][8].  One wave per line, four lines per workgroup; the walk is walk_prefix stopped at the
+// fifth tab.  A column runs from behind the tab in front of it to the next tab, or to the line's end without
+// its '\r'; a column the line does not reach is (line end, 0).  A line offset outside the chunk gives zeros.
+__global__ __launch_bounds__(256) void vcf_cols_span_kernel(const uint8_t* __restrict__ text, long nbytes,
+                                                            const int64_t* __restrict__ line_off, long n_lines,
+                                                            int32_t* __restrict__ spans) {
+  const int lane = threadIdx.x & 63;
+  const long line = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (line >= n_lines) return;
+  const long lo = line_off[line];
+  if (lo < 0 || lo >= nbytes) {
+    if (lane < 8) spans[line * 8 + lane] = 0;
+    return;
+  }
+  long t[5] = {-1, -1, -1, -1, -1}, nl = -1;                   // tabs 1 .. 5 and the newline (-1: not met)
+  int ntabs = 0;
+  for (long p = lo;; p += 64) {
+    const uint8_t c = text_at(text, nbytes, p + lane);
+    uint64_t tm = __ballot(c == '\t');
+    const uint64_t nm = __ballot(c == '\n');
+    if (nm) tm &= (nm & (0 - nm)) - 1;                         // tabs in front of the newline only
+    const int k = __popcll(tm), n0 = ntabs;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+      if (n0 <= i && n0 + k > i) t[i] = p + nth_bit(tm, i - n0);
+    ntabs = n0 + k;
+    if (ntabs >= 5) break;
+    if (nm) {
+      nl = p + (__ffsll((unsigned long long)nm) - 1);
+      break;
+    }
+  }
+  long end = -1;                                               // met only when the fifth tab was not
+  if (nl >= 0) end = (nl > lo && text_at(text, nbytes, nl - 1) == '\r') ? nl - 1 : nl;
+  // column j of 1, 3, 4, 5: from behind tab a (the line start for CHROM) to tab b
+  const long a0[4] = {lo, t[1] + 1, t[2] + 1, t[3] + 1}, b0[4] = {t[0], t[2], t[3], t[4]};
+  const bool reach[4] = {true, t[1] >= 0, t[2] >= 0, t[3] >= 0};
+  int32_t v = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const long a = reach[j] ? a0[j] : end, b = reach[j] && b0[j] >= 0 ? b0[j] : end;
+    if (lane == 2 * j) v = (int32_t)a;
+    if (lane == 2 * j + 1) v = (int32_t)(b - a);
+  }
+  if (lane < 8) spans[line * 8 + lane] = v;
+}
+
+constexpr int CG_SHORT = 16;     // bytes a lane copies itself; a longer string is copied by its whole wave
+
+// Item i = c * n + r is column c (0 .. 3) of record r: its spans[r][2 c .. 2 c + 1] bytes of text go to
+// blob[off[i], off[i + 1]).  A lane owns an item.  An item whose span leaves the text, whose length is not
+// off[i + 1] - off[i], or whose range leaves the blob copies nothing: no store leaves a record's own range.
+__global__ __launch_bounds__(256) void vcf_cols_gather_kernel(const uint8_t* __restrict__ text, long nbytes,
+                                                              const int32_t* __restrict__ spans, long n,
+                                                              const int64_t* __restrict__ off,
+                                                              uint8_t* __restrict__ blob, long blob_bytes) {
+  const int lane = threadIdx.x & 63;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  long src = 0, dst = 0;
+  int len = 0;
+  if (i < 4 * n) {
+    const long c = i / n, r = i - c * n;
+    const long s = spans[r * 8 + 2 * c], l = spans[r * 8 + 2 * c + 1], d0 = off[i], d1 = off[i + 1];
+    if (s >= 0 && l > 0 && s + l <= nbytes && d0 >= 0 && d1 - d0 == l && d1 <= blob_bytes) {
+      src = s;
+      dst = d0;
+      len = (int)l;
+    }
+  }
+  if (len <= CG_SHORT)
+    for (int k = 0; k < len; ++k) blob[dst + k] = text[src + k];
+  uint64_t m = __ballot(len > CG_SHORT);
+  while (m) {                                                  // wave-uniform: one long string per turn
+    const int j = __ffsll((unsigned long long)m) - 1;
+    m &= m - 1;
+    const int l = __shfl(len, j, 64);
+    const long s = __shfl((int)src, j, 64);                    // src < nbytes < 2^31
+    const long d = ((long)__shfl((int)(dst >> 32), j, 64) << 32) | (uint32_t)__shfl((int)dst, j, 64);
+    for (int k = lane; k < l; k += 64) blob[d + k] = text[s + k];
+  }
+}
+
+// the checks of snvrag_vcf_cols_span and snvrag_vcf_cols_gather (reported under the entry's name)
+static int vcf_cols_args(const char* where, const uint8_t* text, int64_t nbytes, int64_t n_lines, const void* index,
+                         const int32_t* spans, const void* out) {
+  SNV_CHECK_AS(where, non_null(text, index, spans, out), "null pointer");
+  SNV_CHECK_AS(where, nbytes >= 1 && nbytes < (1LL << 31), "nbytes must be in [1, 2^31)");
+  SNV_CHECK_AS(where, n_lines >= 0 && n_lines <= nbytes, "n_lines must be in [0, nbytes]");
+  SNV_CHECK_AS(where, aligned(16, text) && aligned(8, index) && aligned(4, spans),
+               "text must be 16-byte aligned, the offsets 8-byte aligned, spans 4-byte aligned");
+  return 0;
+}
+
 static inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace snvrag
@@ -596,6 +695,27 @@ extern "C" int snvrag_vcf_unpack_gt(const uint8_t* alt_bits, const uint8_t* miss
   SNV_CHECK_ARG(sblocks * rblocks < (1LL << 31), "blocks must be below 2^31");
   hipLaunchKernelGGL(vcf_unpack_gt_kernel, dim3((unsigned)(sblocks * rblocks)), dim3(256), 0, as_stream(stream),
                      alt_bits, miss_bits, (long)ld_bits, (int)S, (long)n_sites, (int)sblocks, gt);
+  SNV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int snvrag_vcf_cols_span(const uint8_t* text, int64_t nbytes, const int64_t* line_off, int64_t n_lines,
+                                    int32_t* spans, void* stream) {
+  if (int rc = vcf_cols_args("snvrag_vcf_cols_span", text, nbytes, n_lines, line_off, spans, spans)) return rc;
+  if (n_lines == 0) return 0;
+  hipLaunchKernelGGL(vcf_cols_span_kernel, dim3((unsigned)((n_lines + 3) / 4)), dim3(256), 0, as_stream(stream), text,
+                     (long)nbytes, line_off, (long)n_lines, spans);
+  SNV_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int snvrag_vcf_cols_gather(const uint8_t* text, int64_t nbytes, const int32_t* spans, int64_t n_lines,
+                                      const int64_t* off, uint8_t* blob, int64_t blob_bytes, void* stream) {
+  if (int rc = vcf_cols_args("snvrag_vcf_cols_gather", text, nbytes, n_lines, off, spans, blob)) return rc;
+  SNV_CHECK_ARG(blob_bytes >= 0, "blob_bytes must not be negative");
+  if (n_lines == 0) return 0;
+  hipLaunchKernelGGL(vcf_cols_gather_kernel, dim3((unsigned)((4 * n_lines + 255) / 256)), dim3(256), 0,
+                     as_stream(stream), text, (long)nbytes, spans, (long)n_lines, off, blob, (long)blob_bytes);
   SNV_LAUNCH_CHECK();
   return 0;
 }

@@ -45,7 +45,15 @@ region is not returned.  ``READ_STATS`` counts the members the last call inflate
 Not covered: single-member gzip on the device, ``.csi`` indexes, overlap (REF-length) selection of a region, an
 indexer on the device for files this project did not write (``tbi.index_vcf_bgzf`` is the slow host
 specification), a rank reading only its shard's sample columns, multi-allelic splitting (any allele number > 0 is
-ALT), REF / ALT / ID strings, h5 files.
+ALT; ALT ``A,C`` is carried as written), QUAL / FILTER / INFO and the header lines of an input, h5 files.
+
+``columns=True`` also returns the CHROM, ID, REF and ALT strings of every record (``VcfGenotypes.columns``, a
+``SiteColumns``; ``site_columns_host`` is the specification).  They are cut out on the device, inside the chunk
+pipeline and before the text buffer is recycled: ``snvrag_vcf_cols_span`` walks every line to its fifth tab and
+writes four (start, length) spans, the spans of the kept records are scanned (``torch.cumsum``) and
+``snvrag_vcf_cols_gather`` packs the bytes into one blob per chunk; the blob is allocated by an upper bound (the
+chunk's bytes less 2 S per record) and trimmed to its real size once the next chunk's line count has come back,
+so no host wait is added.  The strings append in file order; the 64-record carry of the code rows does not touch them.
 """
 
 from __future__ import annotations
@@ -167,10 +175,8 @@ def record_flags(line: bytes, n_samples: int):
     return flags, pos, calls
 
 
-def parse_vcf_host(path_or_bytes: Union[str, os.PathLike, bytes]):
-    """(samples, pos int32 [n], gt int8 [n, S, 2]) of a VCF given by path (``.gz`` by its magic bytes) or
-    as bytes: allele numbers (capped at 127), -1 for missing, as ``allel.read_vcf`` documents
-    ``calldata/GT``.  The specification of ``read_vcf``; ``ValueError`` names the 1-based file line."""
+def _host_text(path_or_bytes) -> Tuple[str, bytes]:
+    """(name, the whole text) of a VCF given by path or as bytes, ``.gz`` by its magic bytes."""
     if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
         name, data = "<bytes>", bytes(path_or_bytes)
         if data[:2] == b"\x1f\x8b":
@@ -179,6 +185,14 @@ def parse_vcf_host(path_or_bytes: Union[str, os.PathLike, bytes]):
         name = str(path_or_bytes)
         with _open(path_or_bytes) as fh:
             data = fh.read()
+    return name, data
+
+
+def parse_vcf_host(path_or_bytes: Union[str, os.PathLike, bytes]):
+    """(samples, pos int32 [n], gt int8 [n, S, 2]) of a VCF given by path (``.gz`` by its magic bytes) or
+    as bytes: allele numbers (capped at 127), -1 for missing, as ``allel.read_vcf`` documents
+    ``calldata/GT``.  The specification of ``read_vcf``; ``ValueError`` names the 1-based file line."""
+    name, data = _host_text(path_or_bytes)
     samples, pos, gt = None, [], []
     for lineno, line in enumerate(data.split(b"\n"), 1):
         if samples is None:
@@ -200,6 +214,99 @@ def parse_vcf_host(path_or_bytes: Union[str, os.PathLike, bytes]):
     return samples, np.asarray(pos, np.int32), np.asarray(gt, np.int8).reshape(len(pos), S, 2)
 
 
+COLUMN_NAMES = ("chrom", "id", "ref", "alt")
+COLUMN_FIELDS = (0, 2, 3, 4)               # their 0-based places in a record
+
+
+def record_columns(line: bytes) -> Tuple[bytes, bytes, bytes, bytes]:
+    """(CHROM, ID, REF, ALT) of one record without its newline: the tab-separated columns 1, 3, 4 and 5, the
+    last column of a short line ending in front of a trailing '\\r'; a column the line does not reach is b""."""
+    if line.endswith(b"\r"):
+        line = line[:-1]
+    f = line.split(b"\t")
+    return tuple(f[k] if len(f) > k else b"" for k in COLUMN_FIELDS)
+
+
+class SiteColumns:
+    """CHROM, ID, REF and ALT of ``n`` records as packed bytes: for each name of ``COLUMN_NAMES`` an int64
+    ``<name>_off`` [n + 1] and a uint8 ``<name>_blob`` (host arrays); record r's string is
+    ``blob[off[r]:off[r + 1]]``.  ``chrom(r)`` / ``id(r)`` / ``ref(r)`` / ``alt(r)`` give it as ``bytes``,
+    ``column(name)`` all of them, ``lengths(name)`` and ``ref_len`` the int64 lengths."""
+
+    def __init__(self, parts):
+        """``parts``: (off, blob) per name of ``COLUMN_NAMES``, in that order."""
+        assert len(parts) == len(COLUMN_NAMES)
+        for name, (off, blob) in zip(COLUMN_NAMES, parts):
+            off, blob = np.ascontiguousarray(off, np.int64), np.ascontiguousarray(blob, np.uint8)
+            assert off.ndim == 1 and off.size >= 1 and off[0] == 0 and off[-1] == blob.size
+            setattr(self, name + "_off", off)
+            setattr(self, name + "_blob", blob)
+        self.n = int(self.chrom_off.size) - 1
+        assert all(getattr(self, name + "_off").size == self.n + 1 for name in COLUMN_NAMES)
+
+    @classmethod
+    def from_records(cls, records) -> "SiteColumns":
+        """Of a sequence of (CHROM, ID, REF, ALT) bytes."""
+        parts = []
+        for c in range(len(COLUMN_NAMES)):
+            strings = [r[c] for r in records]
+            off = np.zeros(len(strings) + 1, np.int64)
+            np.cumsum([len(t) for t in strings], out=off[1:])
+            parts.append((off, np.frombuffer(b"".join(strings), np.uint8)))
+        return cls(parts)
+
+    def __len__(self) -> int:
+        return self.n
+
+    def get(self, name: str, r: int) -> bytes:
+        off = getattr(self, name + "_off")
+        if not 0 <= r < self.n:
+            raise IndexError(r)
+        return getattr(self, name + "_blob")[off[r]:off[r + 1]].tobytes()
+
+    def chrom(self, r: int) -> bytes:
+        return self.get("chrom", r)
+
+    def id(self, r: int) -> bytes:
+        return self.get("id", r)
+
+    def ref(self, r: int) -> bytes:
+        return self.get("ref", r)
+
+    def alt(self, r: int) -> bytes:
+        return self.get("alt", r)
+
+    def column(self, name: str) -> List[bytes]:
+        off, blob = getattr(self, name + "_off"), getattr(self, name + "_blob").tobytes()
+        return [blob[off[r]:off[r + 1]] for r in range(self.n)]
+
+    def lengths(self, name: str) -> np.ndarray:
+        return np.diff(getattr(self, name + "_off"))
+
+    @property
+    def ref_len(self) -> np.ndarray:
+        return self.lengths("ref")
+
+
+def site_columns_host(path_or_bytes: Union[str, os.PathLike, bytes]) -> SiteColumns:
+    """CHROM, ID, REF and ALT of every record of a VCF given by path (``.gz`` by its magic bytes) or as bytes:
+    the specification of ``read_vcf(columns=True).columns``.  The line rules of ``parse_vcf_host``: the body
+    begins behind the #CHROM line, zero-length lines ("" and "\\r") vanish, "\\r\\n" ends a line as "\\n"
+    does.  The records are not checked otherwise (``parse_vcf_host`` does that)."""
+    name, data = _host_text(path_or_bytes)
+    records, body = [], False
+    for line in data.split(b"\n"):
+        if not body:
+            body = line.startswith(b"#CHROM")
+            continue
+        if line in (b"", b"\r"):
+            continue
+        records.append(record_columns(line))
+    if not body:
+        raise ValueError(f"{name}: no #CHROM header")
+    return SiteColumns.from_records(records)
+
+
 @dataclass
 class VcfGenotypes:
     """What ``read_vcf`` returns.  ``alt_bits`` / ``miss_bits``: device u8 [2 S, ceil(n_sites / 8)],
@@ -212,6 +319,7 @@ class VcfGenotypes:
     n_sites: int
     any_missing: bool
     phased: bool
+    columns: "SiteColumns" = None          # read_vcf(columns=True): CHROM, ID, REF, ALT of the n_sites records
 
     def gt(self) -> np.ndarray:
         """int8 [n_sites, S, 2]: 0 / 1 (any ALT allele is 1), -1 where missing; unpacked on the device,
@@ -253,8 +361,11 @@ class _ChunkParser:
     """What follows a chunk's text on the device, for either source of the text: line index, parse, and the
     pack of every whole group of 64 records; ``finish`` joins the parts."""
 
-    def __init__(self, path, name, dev, samples, chunk_bytes, force_general, region=None):
+    def __init__(self, path, name, dev, samples, chunk_bytes, force_general, region=None, columns=False):
         import torch
+        # columns: per chunk the lengths (i64 [4 n], column-major) and the trimmed blob of each column; the last
+        # chunk's untrimmed blob with its offsets waits in col_pending until its kernels are known to be done
+        self.columns, self.col_lens, self.col_blobs, self.col_pending = columns, [], [[] for _ in COLUMN_NAMES], None
         self.path, self.name, self.dev, self.samples, self.force_general = path, name, dev, samples, force_general
         # a region read: the records kept per chunk (count, their line offsets, the chunk's place in the span's
         # text) and the span's members (file offset, ISIZE), for the virtual offset an error message names
@@ -281,17 +392,21 @@ class _ChunkParser:
         from .. import kernels as K
         line_off, n_lines = K.vcf_line_index(text, cut, self.max_lines)
         nl = int(n_lines.item())                       # also: the chunk's upload has left the host
+        self._trim()                                   # and the previous chunk's gather is done
         if nl > self.max_lines:                        # a line shorter than any record
             if self.region is None:                    # (a region read does not scan the file for the line)
                 parse_vcf_host(self.path)
             raise ValueError(f"{self.name}: a body line is shorter than a record of {self.S} samples")
         if nl:
             p, f = K.vcf_parse_gt(text, cut, line_off, nl, self.S, self.codes[self.carry:], self.force_general)
+            spans, lo = (K.vcf_cols_span(text, cut, line_off, nl) if self.columns else None), 0
             if self.region is not None:
-                p, f, nl = self._select(p, f, line_off, nl)
+                p, f, nl, lo = self._select(p, f, line_off, nl)
         if nl:
             self.pos_parts.append(p)
             self.flag_parts.append(f)
+            if self.columns:
+                self._gather(text, cut, spans[lo:lo + nl])
         parsed_event.record(stream)
         total = self.carry + nl
         full = total if last else total // 64 * 64
@@ -318,7 +433,51 @@ class _ChunkParser:
             self.codes[self.carry:self.carry + hi - lo].copy_(self.codes[self.carry + lo:self.carry + hi].clone())
         if hi > lo:
             self.kept.append((hi - lo, line_off[lo:hi].clone(), self.text_base))
-        return p[lo:hi], f[lo:hi], hi - lo
+        return p[lo:hi], f[lo:hi], hi - lo, lo
+
+    def _gather(self, text, cut, spans):
+        """The strings of the kept records' spans packed into one blob, the four columns one behind the other.
+        A valid record spends at least 2 S bytes on its cells, so the blob is bounded without a host wait; a
+        record that breaks the bound is flagged by the parse and copied nowhere."""
+        import torch
+        from .. import kernels as K
+        n = spans.shape[0]
+        lens = spans[:, 1::2].t().reshape(-1).to(torch.int64)          # item c n + r: column c of record r
+        off = torch.zeros(4 * n + 1, device=self.dev, dtype=torch.int64)
+        torch.cumsum(lens, 0, out=off[1:])
+        blob = torch.empty(max(cut - 2 * self.S * n, 16), device=self.dev, dtype=torch.uint8)
+        K.vcf_cols_gather(text, cut, spans, off, blob)
+        self.col_lens.append(lens.view(4, n))
+        self.col_pending = (blob, off[::n])
+
+    def _trim(self):
+        """The pending blob cut into its four columns at their real sizes.  Called where the kernels that wrote
+        it are known to have finished, so the five offsets come back without a wait of their own."""
+        if self.col_pending is None:
+            return
+        blob, bounds = self.col_pending
+        b = [min(int(v), blob.numel()) for v in bounds.cpu().tolist()]
+        for c in range(len(COLUMN_NAMES)):
+            self.col_blobs[c].append(blob[b[c]:b[c + 1]].clone())
+        self.col_pending = None
+
+    def _site_columns(self) -> "SiteColumns":
+        """The parts joined: per column one copy of the offsets and one of the blob to the host."""
+        import torch
+        parts = []
+        for c in range(len(COLUMN_NAMES)):
+            off = torch.zeros(self.n_records + 1, device=self.dev, dtype=torch.int64)
+            if self.n_records:
+                torch.cumsum(torch.cat([l[c] for l in self.col_lens]), 0, out=off[1:])
+                blob = torch.cat(self.col_blobs[c])
+            else:
+                blob = torch.zeros(0, device=self.dev, dtype=torch.uint8)
+            off, blob = off.cpu().numpy(), blob.cpu().numpy()
+            if off[-1] != blob.size:                   # every record passed the flags: cannot happen
+                raise RuntimeError(f"{self.name}: the {COLUMN_NAMES[c].upper()} strings take {int(off[-1])} bytes, "
+                                   f"{blob.size} were gathered")
+            parts.append((off, blob))
+        return SiteColumns(parts)
 
     def _region_error(self, r, pos, flags) -> ValueError:
         """The file line of a region's record is not known without a full scan: POS and the virtual offset."""
@@ -349,6 +508,7 @@ class _ChunkParser:
             alt_bits = torch.zeros(2 * S, 0, device=dev, dtype=torch.uint8)
             miss_bits = torch.zeros(2 * S, 0, device=dev, dtype=torch.uint8)
         torch.cuda.synchronize(dev)
+        self._trim()
         bad = np.flatnonzero(flags & np.uint32(FLAG_ERRORS | FLAG_OFFSET))
         if bad.size:
             r = int(bad[0])
@@ -359,11 +519,12 @@ class _ChunkParser:
             raise flag_error(name, _record_line(self.path, r), int(flags[r]) & FLAG_ERRORS)
         seen = int(np.bitwise_or.reduce(flags >> np.uint32(8))) if flags.size else 0
         return VcfGenotypes(self.samples, pos.astype(np.int32, copy=False), alt_bits, miss_bits, self.n_records,
-                            bool(seen & (CODE_MISS1 | CODE_MISS2)), not seen & CODE_SLASH)
+                            bool(seen & (CODE_MISS1 | CODE_MISS2)), not seen & CODE_SLASH,
+                            self._site_columns() if self.columns else None)
 
 
 def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general: bool = False,
-             inflate: str = None, region=None) -> VcfGenotypes:
+             inflate: str = None, region=None, columns: bool = False) -> VcfGenotypes:
     """POS and GT of the VCF at ``path``, the body parsed on ``device``.  ``.gz`` / BGZF is inflated on the host
     (streaming), or with ``inflate="device"`` (``None``: ``DEFAULT_INFLATE``) on the GPU when the file is BGZF.
     ``force_general`` sends every line through the general parse path (same result).  ``ValueError``: what
@@ -377,7 +538,11 @@ def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general
     table path) and parsed.  A name the index does not hold, or an empty span, gives an empty result.  An error
     message of a region read names the record's POS and virtual offset in place of the file line.  The record
     flags are checked for the region's records only; a line of the span that is shorter than any record raises
-    whether or not it lies in the region (it is met before POS is known), without the file line."""
+    whether or not it lies in the region (it is met before POS is known), without the file line.
+
+    ``columns=True``: the result's ``columns`` holds the CHROM, ID, REF and ALT bytes of the returned records
+    (``SiteColumns``; of a region read, of the kept records only), cut out of the text on the device.  Every
+    other field is what ``columns=False`` gives, bit for bit."""
     import torch
     from .. import native as N
     N.require_gpu()
@@ -389,11 +554,11 @@ def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general
     name, dev = str(path), torch.device(device)
     READ_STATS["members_inflated"] = 0
     if region is not None:
-        return _read_vcf_region(path, name, dev, chunk_bytes, force_general, mode, region)
+        return _read_vcf_region(path, name, dev, chunk_bytes, force_general, mode, region, columns)
     if mode == "device":
         from .bgzf import is_bgzf
         if is_bgzf(path):
-            return _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general)
+            return _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general, columns=columns)
         print(f"{name}: not a BGZF file, inflate=\"device\" does not apply: reading it on the host")
     with _open(path) as fh:
         if not isinstance(fh, gzip.GzipFile):               # no buffer larger than the file itself
@@ -408,7 +573,8 @@ def read_vcf(path, device, chunk_bytes: int = DEFAULT_CHUNK_BYTES, force_general
                 raise ValueError(f"{name}: a record in front of the #CHROM header")
         if samples is None:
             raise ValueError(f"{name}: no #CHROM header")
-        return _parse_text(fh, _ChunkParser(path, name, dev, samples, chunk_bytes, force_general), chunk_bytes)
+        return _parse_text(fh, _ChunkParser(path, name, dev, samples, chunk_bytes, force_general, columns=columns),
+                           chunk_bytes)
 
 
 def _parse_text(fh, parser, chunk_bytes) -> VcfGenotypes:
@@ -593,7 +759,7 @@ class _SpanText:
         return n
 
 
-def _read_vcf_region(path, name, dev, chunk_bytes, force_general, mode, region) -> VcfGenotypes:
+def _read_vcf_region(path, name, dev, chunk_bytes, force_general, mode, region, columns=False) -> VcfGenotypes:
     """``read_vcf(region=...)``: the header from the front of the file, the body from the one span of virtual
     offsets ``tbi.query`` gives for the region.  Raw bytes are read from the member at ``v_lo >> 16`` to the end
     of the member at ``v_hi >> 16`` (its length from its own header; not read when ``v_hi & 0xffff`` is 0); the
@@ -611,7 +777,7 @@ def _read_vcf_region(path, name, dev, chunk_bytes, force_general, mode, region) 
         samples, _, _ = _bgzf_header(path, name, fh)
         span = tbi.query(index, seq, first - 1, last) if first <= last else None
         if span is None:
-            return _ChunkParser(path, name, dev, samples, 64, force_general).finish()
+            return _ChunkParser(path, name, dev, samples, 64, force_general, columns=columns).finish()
         (start, cut_off), (skip, cut) = (v >> 16 for v in span), (v & 0xffff for v in span)
         end = cut_off
         if cut:                                            # the last member's length, from its own header
@@ -634,14 +800,16 @@ def _read_vcf_region(path, name, dev, chunk_bytes, force_general, mode, region) 
                 raise _bgzf_error(name, start + used, f"truncated (does {name}.tbi describe this file?)")
             chunk_bytes = min(chunk_bytes, max(64, sum(blk.isize for blk in blocks) + 64))
             raw = _RawSpan(io.BytesIO(data), 0, len(data))
-        parser = _ChunkParser(path, name, dev, samples, chunk_bytes, force_general, region=(seq, first, last))
+        parser = _ChunkParser(path, name, dev, samples, chunk_bytes, force_general, region=(seq, first, last),
+                              columns=columns)
         if mode == "device":
             return _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general, parser,
                                             (raw, start, end, skip, cut_off, cut))
         return _parse_text(_SpanText(raw, name, start, skip, cut_off, cut, parser), parser, chunk_bytes)
 
 
-def _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general, parser=None, span=None) -> VcfGenotypes:
+def _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general, parser=None, span=None,
+                             columns=False) -> VcfGenotypes:
     """``read_vcf`` of a BGZF file with the blocks inflated on the device (``span``: of a region read, the raw
     bytes, their file range, and where the text begins in the first member and ends in the last).  Per chunk:
     raw bytes are read into
@@ -674,7 +842,7 @@ def _read_vcf_device_inflate(path, name, dev, chunk_bytes, force_general, parser
             uploaded = [torch.cuda.Event(), torch.cuda.Event()]
             parsed = [torch.cuda.Event(), torch.cuda.Event()]
             if parser is None:
-                parser = _ChunkParser(path, name, dev, samples, chunk_bytes, force_general)
+                parser = _ChunkParser(path, name, dev, samples, chunk_bytes, force_general, columns=columns)
             rest = np.zeros(0, np.uint8)           # raw bytes read and not yet taken: whole blocks and a partial one
             base = off0                            # file offset of rest[0]
             tail_len, eof, c, text_seen = 0, False, 0, 0

@@ -99,7 +99,17 @@ def parse_args(argv=None):
                    help="the .panel file of --ref_panel (a .vcf / .vcf.gz): Freq.npy and the pos / pop maps are counted "
                         "from the panel's genotypes on the GPU (dataset/panel_stats.py) in place of --freq_path, "
                         "--pop_path, --pos_path and --type_path; nothing is written (build_panel_stats writes them)")
+    p.add_argument("--vcf_site_columns", action="store_true",
+                   help="carry CHROM, ID, REF and ALT of --ref_panel (a .vcf / .vcf.gz, read once with its strings cut "
+                        "out on the GPU) and the sample names of a VCF --infer_dataset into imputed.vcf; the panel's "
+                        "CHROM replaces --chrom; with --truth_vcf, a truth record with other alleles is not scored")
     args = p.parse_args(argv)
+    if args.vcf_site_columns:
+        if args.synthetic:
+            p.error("--vcf_site_columns does not go with --synthetic")
+        from .dataset.vcf_reader import is_vcf_path
+        if not args.ref_panel or not is_vcf_path(args.ref_panel):
+            p.error("--vcf_site_columns needs --ref_panel, a .vcf or .vcf.gz file")
     if args.vcf_index and not args.vcf_bgzf:
         p.error("--vcf_index needs --vcf_bgzf: a .tbi indexes a bgzipped file")
     if args.ref_panel_pops:
@@ -172,9 +182,9 @@ class _BgzfText:
 
 
 def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, bgzf=False, info=None,
-              index=False):
+              index=False, ids=None):
     """VCF 4.2 records of the imputed sites (utils.py:378-479 layout: FORMAT GT:HDS:GP:DS,
-    ID '.', REF/ALT '.' unless given, QUAL 0, FILTER PASS).  ``pos_flag`` selects the sites
+    ID and REF/ALT '.' unless ``ids`` / ``ref`` / ``alt`` give one string per site row, QUAL 0, FILTER PASS).  ``pos_flag`` selects the sites
     written (the reference writes only flagged = imputed positions, infer_embedding_rag.py:237).
     ``bgzf``: the same text as a bgzipped file (BGZF members of 0xff00 bytes, zlib level 6, the EOF block).
     ``info``: one INFO string per site row (``quality.info_strings``: AF, DR2, R2, IMP) in place of '.', and the
@@ -206,9 +216,10 @@ def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, al
             r = ref[i] if ref is not None else "."
             a = alt[i] if alt is not None else "."
             inf = info[i] if info is not None else "."
+            d = ids[i] if ids is not None else "."
             if index:
                 voff.append(f.tell_virtual())
-            f.write(f"{chrom}\t{int(pos[i])}\t.\t{r}\t{a}\t0.0\tPASS\t{inf}\tGT:HDS:GP:DS\t" +
+            f.write(f"{chrom}\t{int(pos[i])}\t{d}\t{r}\t{a}\t0.0\tPASS\t{inf}\tGT:HDS:GP:DS\t" +
                     "\t".join(vcf_cells(h1[i], h2[i], gt[i])) + "\n")
     if index:
         voff.append(f.tell_virtual())                      # closed: the EOF block's offset
@@ -226,13 +237,17 @@ def build_dataset(args):
         from .dataset.dataset import PanelData
         vocab = WordVocab(list(PanelData.from_file(args.infer_panel).pop_class_dict.keys()))
         extra = {}
-        if getattr(args, "ref_panel_pops", None):
-            # the panel VCF is read once: the same bit rows give the tables here and the kNN index later
+        want_columns = bool(getattr(args, "vcf_site_columns", False))
+        if getattr(args, "ref_panel_pops", None) or want_columns:
+            # the panel VCF is read once: the same bit rows give the tables here and the kNN index later, and
+            # with --vcf_site_columns the same read cuts out the strings of the output's CHROM / ID / REF / ALT
             from .dataset import vcf_reader
-            from .dataset.panel_stats import build_tables
             dev = torch.device("cuda", torch.cuda.current_device())
-            panel_vg = vcf_reader.read_vcf(args.ref_panel, dev)
-            extra = dict(tables=build_tables(panel_vg, args.ref_panel_pops, dev), ref_panel_vcf=panel_vg)
+            panel_vg = vcf_reader.read_vcf(args.ref_panel, dev, **({"columns": True} if want_columns else {}))
+            extra = dict(ref_panel_vcf=panel_vg)
+            if getattr(args, "ref_panel_pops", None):
+                from .dataset.panel_stats import build_tables
+                extra["tables"] = build_tables(panel_vg, args.ref_panel_pops, dev)
         ds = EmbeddingRAGInferDataset.from_file(vocab, args.infer_dataset, args.infer_panel, args.freq_path,
                                                 args.type_path, args.pop_path, args.pos_path,
                                                 ref_vcf_path=args.ref_panel, window_len=args.window_len,
@@ -372,11 +387,54 @@ def _empty_rows(key, dev, k):
     return torch.zeros(shape, device=dev, dtype=dt)
 
 
-def site_quality(args, ds, dev, src, flag):
+def panel_site_columns(ds, default_chrom: str):
+    """``--vcf_site_columns``: the output's CHROM and, per row of ``ds.ori_pos``, the ID, REF and ALT strings of
+    the first panel record at that POS (the rule ``_build_embedding_indexes`` maps genotypes by); '.' where the
+    panel VCF does not hold the site.  Returns dict(chrom, ids, ref, alt (lists of str), rows (the panel record
+    of each row, -1 none), columns (the panel's ``SiteColumns``)).  The bytes are decoded with the encoding the
+    writers encode with.  ``ValueError``: two CHROM values among the mapped records, or a record that does
+    not decode (names its POS)."""
+    import locale
+    vg = ds.ref_panel_vcf
+    if vg is None or vg.columns is None:
+        raise ValueError("--vcf_site_columns: the panel was not read from a VCF with columns=True")
+    cols, encoding = vg.columns, locale.getpreferredencoding(False)
+    first = {}
+    for i, p in enumerate(np.asarray(vg.pos).tolist()):
+        first.setdefault(p, i)
+    ori_pos = np.asarray(ds.ori_pos).tolist()
+    rows = np.array([first.get(p, -1) for p in ori_pos], dtype=np.int64)
+    chrom, out = None, dict(ids=[], ref=[], alt=[])
+    for p, r in zip(ori_pos, rows.tolist()):
+        if r < 0:
+            for v in out.values():
+                v.append(".")
+            continue
+        try:
+            c = cols.chrom(r).decode(encoding)
+            strings = [cols.get(name, r).decode(encoding) for name in ("id", "ref", "alt")]
+        except UnicodeDecodeError as e:
+            raise ValueError(f"--vcf_site_columns: the panel record at POS {p} does not decode as {encoding}: {e}") from None
+        if chrom is None:
+            chrom = c
+        elif c != chrom:
+            raise ValueError(f"--vcf_site_columns: the panel records at the imputed sites name two sequences, "
+                             f"{chrom!r} and {c!r} (POS {p}); one output file holds one CHROM")
+        for v, t in zip(out.values(), strings):
+            v.append(t)
+    return dict(out, chrom=default_chrom if chrom is None else chrom, rows=rows, columns=cols)
+
+
+def site_quality(args, ds, dev, src, flag, chrom=None, site_cols=None):
     """``--vcf_info`` / ``--truth_vcf`` on rank 0: the per-site sums of ``src`` (h1 / h2 / gt, device tensors or
     host arrays) by the kernel (quality.py).  Returns the INFO strings for the writers (None without
     ``--vcf_info``); with ``--truth_vcf`` also writes quality.npz and accuracy.tsv and prints the ALL row.  The
-    imputed sites (``flag``, what the VCF writer selects) that the truth file holds are the ones evaluated."""
+    imputed sites (``flag``, what the VCF writer selects) that the truth file holds are the ones evaluated.
+    ``chrom``: the sequence ``--truth_region imputed`` asks for (default ``--chrom``).  ``site_cols``
+    (``panel_site_columns``, with ``--vcf_site_columns``): the truth file is read with its strings, and a matched
+    site whose (REF, ALT) differs from the panel's is not scored (``truth_row`` -1; counted in quality.npz's
+    ``allele_mismatch`` and on the printed ALL line)."""
+    chrom = args.chrom if chrom is None else chrom
     from . import kernels as K
     from . import quality as Q
     S = src["h1"].shape[1]
@@ -387,11 +445,20 @@ def site_quality(args, ds, dev, src, flag):
         region = None
         if args.truth_region == "imputed":               # through the .tbi: only the members that span touches
             imputed = ori_pos[np.asarray(flag, bool)]
-            region = (args.chrom, int(imputed.min()), int(imputed.max())) if imputed.size else (args.chrom, 1, 0)
-        tv = read_vcf(args.truth_vcf, dev, region=region)
+            region = (chrom, int(imputed.min()), int(imputed.max())) if imputed.size else (chrom, 1, 0)
+        tv = read_vcf(args.truth_vcf, dev, region=region, **({} if site_cols is None else {"columns": True}))
         vg = getattr(ds, "vcf_genotypes", None)
         row, col = Q.truth_maps(tv, ori_pos, None if vg is None else list(vg.samples), n_samples=S)
         row = np.where(flag, row, -1).astype(np.int32)
+        extra = {}
+        if site_cols is not None:                        # the same position, other alleles: another variant
+            pc, tc, mismatch = site_cols["columns"], tv.columns, 0
+            for i in np.flatnonzero((row >= 0) & (site_cols["rows"] >= 0)).tolist():
+                r, t = int(site_cols["rows"][i]), int(row[i])
+                if (pc.ref(r), pc.alt(r)) != (tc.ref(t), tc.alt(t)):
+                    row[i] = -1
+                    mismatch += 1
+            extra["allele_mismatch"] = np.int64(mismatch)
         if tv.n_sites and (row >= 0).any():
             truth = K.vcf_unpack_gt(tv.alt_bits, tv.miss_bits, tv.n_sites)      # device i8, no host round trip
     est, acc, table = Q.site_stats(src["h1"], src["h2"], src["gt"], truth, row, col, device=dev)
@@ -408,12 +475,13 @@ def site_quality(args, ds, dev, src, flag):
         np.savez_compressed(os.path.join(args.output_path, "quality.npz"), pos=ori_pos, flag=flag, est=est, af=af,
                             r2=r2, dr2=dr2, acc=acc, table=table, truth_row=row, maf=maf, acc_n=site["n"],
                             acc_r2=site["r2"], concordance=site["concordance"],
-                            nonref_concordance=site["nonref_concordance"])
+                            nonref_concordance=site["nonref_concordance"], **extra)
         text = Q.accuracy_tsv(rows)
         with open(os.path.join(args.output_path, "accuracy.tsv"), "w") as f:
             f.write(text)
         print("accuracy vs truth  " + text.splitlines()[0].replace("\t", " "), flush=True)
-        print("accuracy vs truth  " + text.splitlines()[-1].replace("\t", " "), flush=True)
+        print("accuracy vs truth  " + text.splitlines()[-1].replace("\t", " ") +
+              "".join(f"  {k}={int(v)}" for k, v in extra.items()), flush=True)
     return Q.info_strings(af, r2, dr2) if args.vcf_info and not args.no_vcf else None
 
 
@@ -464,23 +532,34 @@ def infer(argv=None):
                         pos=np.asarray(ds.ori_pos))
     flag = mask[:, 0].astype(bool)
     info = None
+    chrom, site_cols, written = args.chrom, None, {}
+    if args.vcf_site_columns:
+        site_cols = panel_site_columns(ds, args.chrom)
+        chrom = site_cols["chrom"]
+        if chrom != args.chrom:
+            print(f"--vcf_site_columns: CHROM is the panel's {chrom!r}, not --chrom {args.chrom!r}", flush=True)
+        written = dict(ids=site_cols["ids"], ref=site_cols["ref"], alt=site_cols["alt"])
     if want_quality:
         # in place from the scatter path's device arrays when there are any, else the host arrays through the
         # chunked upload (several ranks: the gathered ones)
-        info = site_quality(args, ds, dev, site_dev if site_dev is not None else dict(h1=h1, h2=h2, gt=gt), flag)
+        info = site_quality(args, ds, dev, site_dev if site_dev is not None else dict(h1=h1, h2=h2, gt=gt), flag,
+                            chrom, site_cols)
     if not args.no_vcf:
         samples = [f"S{i}" for i in range(h1.shape[1])]
+        target = getattr(ds, "vcf_genotypes", None)
+        if args.vcf_site_columns and target is not None and len(target.samples) == len(samples):
+            samples = list(target.samples)
         vcf_path = os.path.join(args.output_path, "imputed.vcf.gz" if args.vcf_bgzf else "imputed.vcf")
         if args.vcf_writer == "device":
             # in place from the scatter path's device arrays when there are any, else the host arrays
             # (several ranks: the gathered ones) uploaded chunk by chunk
             src = site_dev if site_dev is not None else dict(h1=h1, h2=h2, gt=gt)
-            write_vcf_device(vcf_path, args.chrom, ds.ori_pos, src["h1"], src["h2"], src["gt"], samples,
-                             pos_flag=flag, device=dev, bgzf=args.vcf_bgzf, info=info, index=args.vcf_index)
+            write_vcf_device(vcf_path, chrom, ds.ori_pos, src["h1"], src["h2"], src["gt"], samples,
+                             pos_flag=flag, device=dev, bgzf=args.vcf_bgzf, info=info, index=args.vcf_index, **written)
             src = None
         else:
-            write_vcf(vcf_path, args.chrom, ds.ori_pos, h1, h2, gt, samples, pos_flag=flag, bgzf=args.vcf_bgzf,
-                      info=info, index=args.vcf_index)
+            write_vcf(vcf_path, chrom, ds.ori_pos, h1, h2, gt, samples, pos_flag=flag, bgzf=args.vcf_bgzf,
+                      info=info, index=args.vcf_index, **written)
     site_dev = None                    # the device result arrays are freed after the last reader
     print(f"imputed {len(ds)} sample-windows in {res['seconds']:.2f}s "
           f"({res['masked_snvs'] / res['seconds']:.0f} masked SNVs/s)", flush=True)

@@ -914,6 +914,37 @@ def vcf_unpack_gt(alt_bits: torch.Tensor, miss_bits: torch.Tensor, n_sites: int)
     return gt
 
 
+def vcf_cols_span(text: torch.Tensor, nbytes: int, line_off: torch.Tensor, n_lines: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """spans i32 [n_lines, 8]: (start, length) in ``text`` of CHROM, ID, REF and ALT of the lines
+    ``line_off[:n_lines]`` of the chunk (``dataset/vcf_reader.py`` record_columns is the specification; a
+    column the line does not reach has length 0)."""
+    N.require_gpu(text, line_off)
+    _text_ok(text, nbytes)
+    assert line_off.dtype == torch.int64 and line_off.is_contiguous() and line_off.numel() >= n_lines
+    if out is None:
+        out = torch.empty(n_lines, 8, device=text.device, dtype=torch.int32)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == (n_lines, 8)
+    check(N.lib().snvrag_vcf_cols_span(ptr(text), nbytes, ptr(line_off), n_lines, ptr(out), stream_ptr()),
+          "vcf_cols_span")
+    return out
+
+
+def vcf_cols_gather(text: torch.Tensor, nbytes: int, spans: torch.Tensor, off: torch.Tensor,
+                    blob: torch.Tensor) -> None:
+    """The strings of ``spans`` i32 [n, 8] packed into ``blob`` u8: item c * n + r (column c of record r) at
+    ``blob[off[i]:off[i + 1]]``, ``off`` i64 [4 n + 1] the exclusive prefix sum of the lengths in that order.
+    An item that does not fit its range or the blob is not copied."""
+    N.require_gpu(text, spans, off, blob)
+    _text_ok(text, nbytes)
+    n = spans.shape[0]
+    assert spans.dtype == torch.int32 and spans.is_contiguous() and spans.shape == (n, 8)
+    assert off.dtype == torch.int64 and off.is_contiguous() and off.numel() == 4 * n + 1
+    assert blob.dtype == torch.uint8 and blob.dim() == 1 and blob.is_contiguous()
+    check(N.lib().snvrag_vcf_cols_gather(ptr(text), nbytes, ptr(spans), n, ptr(off), ptr(blob), blob.numel(),
+                                         stream_ptr()), "vcf_cols_gather")
+
+
 def panel_counts(alt_bits: torch.Tensor, miss_bits: torch.Tensor, n_sites: int, order: torch.Tensor,
                  pop_start: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Genotype counts i32 [6, 5, n_sites] of the bit rows ``alt_bits`` / ``miss_bits`` u8 [2 S, >= ceil(n_sites / 8)]

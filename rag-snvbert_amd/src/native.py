@@ -174,6 +174,8 @@ _SIGS = {
     "snvrag_vcf_pack_rows": ([vp, i64, i64, i64, i64, vp, vp, i64, vp], C.c_int),
     "snvrag_panel_gather_bits": ([vp, i64, i64, i64, vp, i64, i64, C.c_int, vp, vp], C.c_int),
     "snvrag_vcf_unpack_gt": ([vp, vp, i64, i64, i64, vp, vp], C.c_int),
+    "snvrag_vcf_cols_span": ([vp, i64, vp, i64, vp, vp], C.c_int),
+    "snvrag_vcf_cols_gather": ([vp, i64, vp, i64, vp, vp, i64, vp], C.c_int),
     "snvrag_panel_counts": ([vp, vp, i64, i64, i64, vp, vp, i64, vp, vp], C.c_int),
     "snvrag_bgzf_inflate": ([vp, i64, vp, vp, i64, vp, i64, vp, vp], C.c_int),
     "snvrag_text_last_newline": ([vp, i64, vp, vp], C.c_int),

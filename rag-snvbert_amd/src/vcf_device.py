@@ -70,11 +70,11 @@ def header_lines(samples, info: bool = False) -> str:
             "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join(samples) + "\n")
 
 
-def site_prefixes(chrom, pos, pos_flag=None, ref=None, alt=None, encoding=None, info=None):
+def site_prefixes(chrom, pos, pos_flag=None, ref=None, alt=None, encoding=None, info=None, ids=None):
     """(rows int32 [n_lines], blob bytes, prefix_off int32 [n_lines + 1]): the selected site rows
     (``pos_flag`` as ``write_vcf`` reads it) and their line prefixes — everything ``write_vcf`` puts in
     front of the first cell, the tab included — concatenated.  ``info``: the INFO string of every site row
-    (``write_vcf(info=...)``), '.' without it."""
+    (``write_vcf(info=...)``), '.' without it; ``ids``: the ID string of every site row, '.' without it."""
     encoding = encoding or locale.getpreferredencoding(False)      # what open(path, "w") encodes with
     rows, parts, off = [], [], [0]
     for i in range(len(pos)):
@@ -83,7 +83,8 @@ def site_prefixes(chrom, pos, pos_flag=None, ref=None, alt=None, encoding=None, 
         r = ref[i] if ref is not None else "."
         a = alt[i] if alt is not None else "."
         inf = info[i] if info is not None else "."
-        b = f"{chrom}\t{int(pos[i])}\t.\t{r}\t{a}\t0.0\tPASS\t{inf}\tGT:HDS:GP:DS\t".encode(encoding)
+        d = ids[i] if ids is not None else "."
+        b = f"{chrom}\t{int(pos[i])}\t{d}\t{r}\t{a}\t0.0\tPASS\t{inf}\tGT:HDS:GP:DS\t".encode(encoding)
         rows.append(i)
         parts.append(b)
         off.append(off[-1] + len(b))
@@ -119,7 +120,8 @@ def _host(a):
 
 
 def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, device=None,
-                     chunk_bytes: int = DEFAULT_CHUNK_BYTES, bgzf: bool = False, info=None, index: bool = False) -> bool:
+                     chunk_bytes: int = DEFAULT_CHUNK_BYTES, bgzf: bool = False, info=None, index: bool = False,
+                     ids=None) -> bool:
     """``write_vcf`` with the records formatted on ``device``: the same file, byte for byte.
 
     ``bgzf``: the file is bgzipped.  Each chunk's text is deflated into BGZF members of 0xff00 bytes and packed
@@ -129,7 +131,8 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     block.  It inflates to the plain file byte for byte; the fallback below then writes a bgzipped file too.
 
     ``info``: one INFO string per site row, as ``write_vcf(info=...)``: it takes the place of '.' in the line
-    prefixes (host-built, of any width) and adds the four ##INFO header lines.
+    prefixes (host-built, of any width) and adds the four ##INFO header lines.  ``ids`` / ``ref`` / ``alt``: one
+    string per site row for the ID, REF and ALT columns, as ``write_vcf`` takes them ('.' without).
 
     ``index`` (needs ``bgzf``): also write the tabix index ``path + ".tbi"`` (dataset/tbi.py) without reading the
     file back.  The byte offset of every line in its chunk's text is known on the host; each chunk's member lengths
@@ -166,7 +169,7 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
             raise ValueError("index=True needs bgzf=True: a .tbi indexes a bgzipped file")
         from .dataset import tbi
         beg, end = tbi.vcf_intervals(pos, flag, ref)
-    rows, blob, prefix_off = site_prefixes(chrom, pos, flag, ref, alt, info=info)
+    rows, blob, prefix_off = site_prefixes(chrom, pos, flag, ref, alt, info=info, ids=ids)
     length = line_lengths(prefix_off, S)
     chunks = plan_chunks(length, chunk_bytes)
     if bgzf:
@@ -295,5 +298,5 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     print("write_vcf_device: a value does not fit the fixed-width cell (NaN, infinite, negative or >= 9.9995); "
           "the host writer writes the file", flush=True)
     write_vcf(path, chrom, pos, _host(h1), _host(h2), _host(gt), samples, pos_flag=flag, ref=ref, alt=alt, bgzf=bgzf,
-              info=info, index=index)
+              info=info, index=index, ids=ids)
     return False

@@ -2,6 +2,7 @@
 
   python tools/vcf_read_micro.py [SITESxSAMPLES]      default 4096x2000
   python tools/vcf_read_micro.py --inflate [SITESxSAMPLES]     the BGZF twins: host zlib against the device inflate
+  python tools/vcf_read_micro.py --columns [SITESxSAMPLES]     read_vcf with and without columns=True, and its kernels
 
 Writes a GT-only file (every line fixed-width) and a GT:DS:GP file (every line on the general path) from
 seeded 0/1 arrays into a local temporary directory, then times
@@ -137,11 +138,70 @@ def inflate_arm(files, n, S, gt):
               f"{blocks[one].isize} bytes) alone {t_one:.3f} ms, last newline {t_nl:.3f} ms")
 
 
+def columns_arm(path, n, S):
+    """read_vcf of the GT file with columns=False and columns=True, alternating for ROUNDS rounds (min / median /
+    max: the spread is the run-to-run noise a difference has to exceed); then, on the file's body as one resident
+    chunk, the two site-column kernels and the scan between them beside snvrag_vcf_parse_gt.  On a build whose
+    read_vcf has no ``columns`` only the columns=False rows are printed (the same rows, for a comparison)."""
+    import inspect
+    from src import kernels as K
+    from src.dataset import vcf_reader as V
+    ROUNDS = 7
+    modes = [False] + ([True] if "columns" in inspect.signature(V.read_vcf).parameters else [])
+    read = lambda m: V.read_vcf(path, DEV, **({"columns": True} if m else {}))
+    times = {m: [] for m in modes}
+    for m in modes:
+        read(m)                                                  # warm
+    for _ in range(ROUNDS):
+        for m in modes:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            vg = read(m)
+            times[m].append(time.perf_counter() - t0)
+            assert vg.n_sites == n
+    size = os.path.getsize(path)
+    for m in modes:
+        t = sorted(times[m])
+        print(f"read_vcf columns={m!s:<5} {size / 1e6:7.1f} MB of text, {n} x {S}: min {t[0]:.4f} s, median "
+              f"{t[len(t) // 2]:.4f} s, max {t[-1]:.4f} s over {ROUNDS} alternating rounds")
+    if len(modes) == 1:
+        print("this build's read_vcf has no columns=: nothing else to time")
+        return
+    with open(path, "rb") as fh:
+        head = b"".join(fh.readline() for _ in range(2 + HOST_LINES))
+    want = V.site_columns_host(head)
+    for name in V.COLUMN_NAMES:
+        assert vg.columns.column(name)[:HOST_LINES] == want.column(name), name
+    assert len(vg.columns) == n
+    over = sorted(times[True])[ROUNDS // 2] - sorted(times[False])[ROUNDS // 2]
+    print(f"columns=True costs {over * 1e3:+.2f} ms at the median ({100 * over / sorted(times[False])[ROUNDS // 2]:+.1f} %); "
+          f"the spread of columns=False alone is {(max(times[False]) - min(times[False])) * 1e3:.2f} ms")
+    text, nbytes = body_chunk(path)
+    line_off, n_lines = K.vcf_line_index(text, nbytes, n)
+    codes = torch.empty(n, (S + 3) // 4 * 4, device=DEV, dtype=torch.uint8)
+    t_parse = events_ms(lambda: K.vcf_parse_gt(text, nbytes, line_off, n, S, codes))
+    spans = K.vcf_cols_span(text, nbytes, line_off, n)
+    t_span = events_ms(lambda: K.vcf_cols_span(text, nbytes, line_off, n, out=spans))
+    off = torch.zeros(4 * n + 1, device=DEV, dtype=torch.int64)
+
+    def scan():
+        torch.cumsum(spans[:, 1::2].t().reshape(-1).to(torch.int64), 0, out=off[1:])
+    t_scan = events_ms(scan)
+    blob = torch.empty(max(int(off[-1].item()), 16), device=DEV, dtype=torch.uint8)
+    t_gather = events_ms(lambda: K.vcf_cols_gather(text, nbytes, spans, off, blob))
+    print(f"  one chunk of {nbytes / 1e6:.1f} MB, {n} lines: snvrag_vcf_parse_gt {t_parse:.3f} ms, snvrag_vcf_cols_span "
+          f"{t_span:.3f} ms, the scan of the lengths (torch) {t_scan:.3f} ms, snvrag_vcf_cols_gather {t_gather:.3f} ms "
+          f"({int(off[-1].item())} bytes of strings)")
+
+
 def main():
     from src.dataset import vcf_reader as V
     inflate = "--inflate" in sys.argv
     if inflate:
         sys.argv.remove("--inflate")
+    columns = "--columns" in sys.argv
+    if columns:
+        sys.argv.remove("--columns")
     n, S = (int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "4096x2000").lower().split("x"))
     rng = np.random.default_rng(0)
     gt = (rng.random((n, S, 2)) < 0.2).astype(np.int8)
@@ -159,6 +219,9 @@ def main():
         V.write_gt_vcf(files["GT:DS:GP"], names, pos, gt, fmt="GT:DS:GP", extra=":1.25:0.100,0.650,0.250")
         if inflate:
             inflate_arm(files, n, S, gt)
+            return
+        if columns:
+            columns_arm(files["GT"], n, S)
             return
         for k in list(files):
             with open(files[k], "rb") as src, gzip.open(files[k] + ".gz", "wb", compresslevel=6) as dst:
