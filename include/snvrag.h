@@ -864,6 +864,27 @@ int snvrag_panel_counts(const uint8_t* alt_bits, const uint8_t* miss_bits, int64
                         int64_t n_sites, const int32_t* order, const int32_t* pop_start, int64_t P,
                         int32_t* counts, void* stream);
 
+/* Typed-site overlay (opt-in: --vcf_sites all; csrc/typed.hip; src/typed_sites.py typed_overlay_host is the
+ * specification): the target's observed genotypes take the place of the model's output in the site-major result
+ * arrays at the sites the target was genotyped at.
+ *   alt_bits, miss_bits  u8 [2 S_target][ld_bits], the snvrag_vcf_pack_rows layout (haplotype h of sample c in row
+ *          2 c + h, record r at bit r & 7 of byte r >> 3), n_target records; any byte alignment of the rows.
+ *   site_row i32 [n]: the target record of each site row;  col i32 [S]: the target sample of each column.  A value
+ *          outside [0, n_target) / [0, S_target) (-1) leaves the row / column untouched and loads nothing.
+ *   h1, h2 f32 [n][S], gt f32 [n][S][4], in / out.  For a mapped row i and column s, with a1, m1 the ALT and
+ *          missing bit of haplotype 0 and a2, m2 those of haplotype 1: if m1 | m2 the cell keeps every byte and
+ *          missing[i] counts it; else h1 = a1, h2 = a2 (0.0f / 1.0f) and gt is one-hot at 2 a1 + a2 (0|0, 0|1,
+ *          1|0, 1|1).  No other byte of h1 / h2 / gt is written.
+ *   missing i32 [n], out: written for every row (cleared on the stream, then integer atomic adds); 0 for a row
+ *          that is not mapped.
+ * No float arithmetic: the result is exact and two launches give the same bits.  All pointers are device
+ * pointers.  Refused: a null pointer, S or S_target outside [1, 2^29), n or n_target < 0, ld_bits >= 2^31 or
+ * 8 ld_bits < n_target, n * S >= 2^40, gt not 16-byte aligned, h1 / h2 / site_row / col / missing not 4-byte
+ * aligned.  n == 0 launches nothing and returns 0. */
+int snvrag_typed_overlay(const uint8_t* alt_bits, const uint8_t* miss_bits, int64_t ld_bits, int64_t n_target,
+                         int64_t S_target, const int32_t* site_row, const int32_t* col, int64_t n, int64_t S,
+                         float* h1, float* h2, float* gt, int32_t* missing, void* stream);
+
 /* Device inflate of BGZF blocks (csrc/inflate.hip; the gzip layer under allel.read_vcf for a bgzipped
  * .vcf.gz).  The decoder is csrc/inflate_core.h; its specification, status for status, is
  * src/dataset/bgzf.py inflate_block_host.

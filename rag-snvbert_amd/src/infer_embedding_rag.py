@@ -19,6 +19,9 @@ file, byte for byte, with the records formatted on the GPU (vcf_device.py, csrc/
 Windows: query windows are INFER_WINDOW_LEN = 1020 sites; ``--index_window_len`` 510
 (default) reproduces the reference's 510-site index windows and infer masks
 (embedding_rag_infer_dataset.py:16), 1020 aligns them with the query windows.
+
+``--vcf_sites all`` writes one record per panel site: the typed sites carry the target's observed genotypes,
+overlaid on the result arrays on the GPU before anything is written (typed_sites.py, csrc/typed.hip).
 """
 
 from __future__ import annotations
@@ -103,7 +106,15 @@ def parse_args(argv=None):
                    help="carry CHROM, ID, REF and ALT of --ref_panel (a .vcf / .vcf.gz, read once with its strings cut "
                         "out on the GPU) and the sample names of a VCF --infer_dataset into imputed.vcf; the panel's "
                         "CHROM replaces --chrom; with --truth_vcf, a truth record with other alleles is not scored")
+    p.add_argument("--vcf_sites", default="imputed", choices=["imputed", "all"],
+                   help="imputed: imputed.vcf holds the sites the target lacks; all: one record per panel site, the "
+                        "typed sites with the target's observed genotypes (overlaid on the GPU, csrc/typed.hip; "
+                        "typed_sites.py) and, with --vcf_info, TYPED in place of IMP; needs --index_window_len equal "
+                        "to --window_len")
     args = p.parse_args(argv)
+    if args.vcf_sites == "all" and args.index_window_len != args.window_len:
+        p.error("--vcf_sites all needs --index_window_len equal to --window_len: with other index windows the mask "
+                "does not describe the sites the target lacks")
     if args.vcf_site_columns:
         if args.synthetic:
             p.error("--vcf_site_columns does not go with --synthetic")
@@ -182,13 +193,14 @@ class _BgzfText:
 
 
 def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, bgzf=False, info=None,
-              index=False, ids=None):
+              index=False, ids=None, typed=False):
     """VCF 4.2 records of the imputed sites (utils.py:378-479 layout: FORMAT GT:HDS:GP:DS,
     ID and REF/ALT '.' unless ``ids`` / ``ref`` / ``alt`` give one string per site row, QUAL 0, FILTER PASS).  ``pos_flag`` selects the sites
     written (the reference writes only flagged = imputed positions, infer_embedding_rag.py:237).
     ``bgzf``: the same text as a bgzipped file (BGZF members of 0xff00 bytes, zlib level 6, the EOF block).
     ``info``: one INFO string per site row (``quality.info_strings``: AF, DR2, R2, IMP) in place of '.', and the
-    four ##INFO header lines that declare them.
+    four ##INFO header lines that declare them.  ``typed`` (``--vcf_sites all``): the header also declares the
+    TYPED flag (``vcf_device.TYPED_HEADER``); no record changes.
     ``index`` (needs ``bgzf``): also write the tabix index ``path + ".tbi"`` (dataset/tbi.py) from the virtual
     offsets the BGZF writer reports around every record: no second pass over the file, and no byte of the file
     itself changes.  A position >= 2^29 raises ``ValueError`` before anything is written."""
@@ -205,6 +217,9 @@ def write_vcf(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, al
         if info is not None:
             from .vcf_device import INFO_HEADER
             f.write(INFO_HEADER)
+        if typed:
+            from .vcf_device import TYPED_HEADER
+            f.write(TYPED_HEADER)
         f.write('##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype (argmax of GP)">\n')
         f.write('##FORMAT=<ID=HDS,Number=2,Type=Float,Description="Haplotype ALT dosages">\n')
         f.write('##FORMAT=<ID=GP,Number=3,Type=Float,Description="Genotype probabilities">\n')
@@ -482,7 +497,39 @@ def site_quality(args, ds, dev, src, flag, chrom=None, site_cols=None):
         print("accuracy vs truth  " + text.splitlines()[0].replace("\t", " "), flush=True)
         print("accuracy vs truth  " + text.splitlines()[-1].replace("\t", " ") +
               "".join(f"  {k}={int(v)}" for k, v in extra.items()), flush=True)
-    return Q.info_strings(af, r2, dr2) if args.vcf_info and not args.no_vcf else None
+    if not (args.vcf_info and not args.no_vcf):
+        return None
+    # --vcf_sites all: every row is written, the typed ones flagged TYPED in place of IMP
+    return Q.info_strings(af, r2, dr2, imputed=flag if getattr(args, "vcf_sites", "imputed") == "all" else None)
+
+
+def overlay_typed_sites(ds, dev, h1, h2, gt, mask, site_dev=None):
+    """``--vcf_sites all`` on rank 0: the target's observed genotypes over the rows of the typed sites
+    (typed_sites.py, csrc/typed.hip).  With ``site_dev`` (the scatter path's device arrays) the overlay runs on
+    them in place and the typed rows of the host arrays h1 / h2 / gt are refreshed from them; else the host arrays
+    go through the kernel in chunks of their typed rows.  Returns (typed bool [n], typed_missing int32 [n]: the
+    cells of each typed row left as the model's output because a call is missing).  ``ValueError`` when the mask
+    of the first sample is not the sites the target lacks (names the first site that differs)."""
+    from . import typed_sites as T
+    flag, need = mask[:, 0].astype(bool), np.asarray(ds.position_needed, bool)
+    if flag.shape != need.shape or (flag != need).any():
+        i = int(np.flatnonzero(flag != need)[0]) if flag.shape == need.shape else min(len(flag), len(need))
+        raise ValueError(f"--vcf_sites all: the mask does not describe the sites the target lacks (first at site row "
+                         f"{i}, POS {int(np.asarray(ds.ori_pos)[i]) if i < len(ds.ori_pos) else -1})")
+    site_row, col = T.target_maps(ds)
+    target = T.target_bit_rows(ds, dev)
+    if site_dev is not None:
+        missing = T.typed_overlay(site_dev["h1"], site_dev["h2"], site_dev["gt"], target, site_row, col)
+        rows = np.flatnonzero(site_row >= 0)
+        d_rows = torch.from_numpy(rows).to(dev)
+        for host, key in ((h1, "h1"), (h2, "h2"), (gt, "gt")):
+            host[rows] = site_dev[key].index_select(0, d_rows).cpu().numpy()
+    else:
+        missing = T.typed_overlay(h1, h2, gt, target, site_row, col, device=dev)
+    typed = ~flag
+    print(f"--vcf_sites all: {int(typed.sum())} typed sites of {len(typed)} carry the target's genotypes; "
+          f"{int(missing.sum())} cells keep the model's output because a call is missing", flush=True)
+    return typed, missing
 
 
 def infer(argv=None):
@@ -520,16 +567,22 @@ def infer(argv=None):
     model = model.to(dev).eval()
     engine_for(model).set_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     want_quality = bool(args.truth_vcf) or (args.vcf_info and not args.no_vcf)
+    all_sites = args.vcf_sites == "all"
     res = run(ds, model, dev, args.infer_batch_size, args.k_retrieve, args.num_workers, args.window_len,
               device_features=args.device_features,
-              keep_site_dev=(args.vcf_writer == "device" and not args.no_vcf) or want_quality)
+              keep_site_dev=(args.vcf_writer == "device" and not args.no_vcf) or want_quality or all_sites)
     h1, h2, gt, mask = res["h1"], res["h2"], res["gt"], res["mask"]
     site_dev = res.pop("site_dev", None)
     if rank != 0:                      # the gathered arrays are written once
         return res
     os.makedirs(args.output_path, exist_ok=True)
+    extra_keys = {}
+    if all_sites:
+        # before anything reads the arrays: the npz, both writers and the quality kernel see the overlaid values
+        typed, typed_missing = overlay_typed_sites(ds, dev, h1, h2, gt, mask, site_dev)
+        extra_keys = dict(typed=typed, typed_missing=typed_missing)
     np.savez_compressed(os.path.join(args.output_path, "imputed.npz"), hap1=h1, hap2=h2, gp=gt, mask=mask,
-                        pos=np.asarray(ds.ori_pos))
+                        pos=np.asarray(ds.ori_pos), **extra_keys)
     flag = mask[:, 0].astype(bool)
     info = None
     chrom, site_cols, written = args.chrom, None, {}
@@ -550,15 +603,18 @@ def infer(argv=None):
         if args.vcf_site_columns and target is not None and len(target.samples) == len(samples):
             samples = list(target.samples)
         vcf_path = os.path.join(args.output_path, "imputed.vcf.gz" if args.vcf_bgzf else "imputed.vcf")
+        if all_sites:                  # one record per row of ds.ori_pos; the TYPED flag is declared where it is used
+            written = dict(written, typed=info is not None)
+        pos_flag = None if all_sites else flag
         if args.vcf_writer == "device":
             # in place from the scatter path's device arrays when there are any, else the host arrays
             # (several ranks: the gathered ones) uploaded chunk by chunk
             src = site_dev if site_dev is not None else dict(h1=h1, h2=h2, gt=gt)
             write_vcf_device(vcf_path, chrom, ds.ori_pos, src["h1"], src["h2"], src["gt"], samples,
-                             pos_flag=flag, device=dev, bgzf=args.vcf_bgzf, info=info, index=args.vcf_index, **written)
+                             pos_flag=pos_flag, device=dev, bgzf=args.vcf_bgzf, info=info, index=args.vcf_index, **written)
             src = None
         else:
-            write_vcf(vcf_path, chrom, ds.ori_pos, h1, h2, gt, samples, pos_flag=flag, bgzf=args.vcf_bgzf,
+            write_vcf(vcf_path, chrom, ds.ori_pos, h1, h2, gt, samples, pos_flag=pos_flag, bgzf=args.vcf_bgzf,
                       info=info, index=args.vcf_index, **written)
     site_dev = None                    # the device result arrays are freed after the last reader
     print(f"imputed {len(ds)} sample-windows in {res['seconds']:.2f}s "

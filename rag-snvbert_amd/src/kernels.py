@@ -972,6 +972,40 @@ def panel_counts(alt_bits: torch.Tensor, miss_bits: torch.Tensor, n_sites: int, 
     return out
 
 
+def typed_overlay(h1: torch.Tensor, h2: torch.Tensor, gt: torch.Tensor, alt_bits: torch.Tensor,
+                  miss_bits: torch.Tensor, n_target: int, site_row: torch.Tensor, col: torch.Tensor,
+                  missing: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The target's observed genotypes written over the site-major result arrays h1 / h2 f32 [n, S], gt f32
+    [n, S, 4] in place (``typed_sites.typed_overlay_host`` is the specification; include/snvrag.h states the
+    rule).  ``alt_bits`` / ``miss_bits`` u8 [2 S_target, ld_bits] hold ``n_target`` records (rows may be views
+    of one row stride); ``site_row`` i32 [n] is the target record of each site row, ``col`` i32 [S] the target
+    sample of each column (-1 or out of range: untouched).  Returns ``missing`` i32 [n]: per site row, the mapped
+    cells left as they were because a call is missing (``missing``: a contiguous i32 [n] to write into)."""
+    N.require_gpu(h1, h2, gt, alt_bits, miss_bits, site_row, col, missing)
+    n, S = h1.shape
+    assert h2.shape == (n, S) and gt.shape == (n, S, 4)
+    assert h1.dtype == h2.dtype == gt.dtype == torch.float32
+    assert h1.is_contiguous() and h2.is_contiguous() and gt.is_contiguous()
+    nb = (n_target + 7) // 8
+    for b in (alt_bits, miss_bits):
+        assert b.dtype == torch.uint8 and b.dim() == 2 and b.shape[0] == alt_bits.shape[0] and b.shape[1] >= nb
+        assert b.shape[1] <= 1 or b.stride(1) == 1
+    S_target = alt_bits.shape[0] // 2
+    assert alt_bits.shape[0] == 2 * S_target and S_target >= 1
+    ld = alt_bits.stride(0) if alt_bits.shape[0] > 1 else max(alt_bits.shape[1], nb)
+    assert all(b.shape[0] <= 1 or b.stride(0) == ld for b in (alt_bits, miss_bits)) and ld >= nb
+    assert site_row.dtype == col.dtype == torch.int32 and site_row.is_contiguous() and col.is_contiguous()
+    assert site_row.numel() == n and col.numel() == S
+    if missing is None:
+        missing = torch.empty(n, device=h1.device, dtype=torch.int32)
+    assert missing.dtype == torch.int32 and missing.is_contiguous() and missing.numel() == n
+    if n == 0:                                     # empty tensors have no address to pass
+        return missing
+    check(N.lib().snvrag_typed_overlay(ptr(alt_bits), ptr(miss_bits), ld, n_target, S_target, ptr(site_row), ptr(col),
+                                       n, S, ptr(h1), ptr(h2), ptr(gt), ptr(missing), stream_ptr()), "typed_overlay")
+    return missing
+
+
 def bgzf_table(in_off, out_off, in_len, isize, crc, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The block table of ``bgzf_inflate`` from five sequences: host i64 [n, 4] = in_off, out_off,
     in_len | isize << 32, crc (into the first rows of ``out`` when given, e.g. a pinned buffer)."""

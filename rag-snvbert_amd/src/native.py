@@ -177,6 +177,7 @@ _SIGS = {
     "snvrag_vcf_cols_span": ([vp, i64, vp, i64, vp, vp], C.c_int),
     "snvrag_vcf_cols_gather": ([vp, i64, vp, i64, vp, vp, i64, vp], C.c_int),
     "snvrag_panel_counts": ([vp, vp, i64, i64, i64, vp, vp, i64, vp, vp], C.c_int),
+    "snvrag_typed_overlay": ([vp, vp, i64, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp], C.c_int),
     "snvrag_bgzf_inflate": ([vp, i64, vp, vp, i64, vp, i64, vp, vp], C.c_int),
     "snvrag_text_last_newline": ([vp, i64, vp, vp], C.c_int),
     "snvrag_bgzf_deflate": ([vp, i64, i64, vp, vp, vp], C.c_int),

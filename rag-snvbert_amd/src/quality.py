@@ -270,11 +270,18 @@ def truth_maps(truth, ori_pos, sample_names=None, n_samples=None):
     return row, np.arange(int(n_samples), dtype=np.int32)
 
 
-def info_strings(af, r2, dr2):
-    """The INFO column of every site: ``AF=%.4f;DR2=%.3f;R2=%.3f;IMP``."""
-    return ["AF=%.4f;DR2=%.3f;R2=%.3f;IMP" % (a, d, r) for a, r, d in zip(np.asarray(af).tolist(),
-                                                                         np.asarray(r2).tolist(),
-                                                                         np.asarray(dr2).tolist())]
+def info_strings(af, r2, dr2, imputed=None):
+    """The INFO column of every site: ``AF=%.4f;DR2=%.3f;R2=%.3f;IMP``.  ``imputed`` (bool per site, with
+    ``--vcf_sites all``): ``IMP`` where true and ``TYPED`` where false; None: every site ``IMP``."""
+    out = ["AF=%.4f;DR2=%.3f;R2=%.3f;IMP" % (a, d, r) for a, r, d in zip(np.asarray(af).tolist(),
+                                                                        np.asarray(r2).tolist(),
+                                                                        np.asarray(dr2).tolist())]
+    if imputed is None:
+        return out
+    imputed = np.asarray(imputed).astype(bool).reshape(-1)
+    if imputed.shape[0] != len(out):
+        raise ValueError("imputed must hold one flag per site")
+    return [s if f else s[:-3] + "TYPED" for s, f in zip(out, imputed.tolist())]
 
 
 def parse_maf_bins(text):

@@ -58,11 +58,15 @@ INFO_HEADER = ('##INFO=<ID=AF,Number=1,Type=Float,Description="Estimated ALT all
                '##INFO=<ID=R2,Number=1,Type=Float,Description="Haplotype-dosage variance over its binomial expectation '
                '(Minimac-style)">\n'
                '##INFO=<ID=IMP,Number=0,Type=Flag,Description="Imputed site">\n')
+# with --vcf_sites all --vcf_info (a record per panel site, IMP or TYPED in its INFO): behind INFO_HEADER
+TYPED_HEADER = '##INFO=<ID=TYPED,Number=0,Type=Flag,Description="Site genotyped in the target">\n'
 
 
-def header_lines(samples, info: bool = False) -> str:
-    """The header ``write_vcf`` writes (same expressions); ``info``: with the four ##INFO lines of ``info=``."""
+def header_lines(samples, info: bool = False, typed: bool = False) -> str:
+    """The header ``write_vcf`` writes (same expressions); ``info``: with the four ##INFO lines of ``info=``;
+    ``typed``: with the ##INFO line of the TYPED flag (``write_vcf(typed=True)``)."""
     return ("##fileformat=VCFv4.2\n##source=rag-snvbert_amd\n" + (INFO_HEADER if info else "") +
+            (TYPED_HEADER if typed else "") +
             '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype (argmax of GP)">\n'
             '##FORMAT=<ID=HDS,Number=2,Type=Float,Description="Haplotype ALT dosages">\n'
             '##FORMAT=<ID=GP,Number=3,Type=Float,Description="Genotype probabilities">\n'
@@ -121,7 +125,7 @@ def _host(a):
 
 def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=None, alt=None, device=None,
                      chunk_bytes: int = DEFAULT_CHUNK_BYTES, bgzf: bool = False, info=None, index: bool = False,
-                     ids=None) -> bool:
+                     ids=None, typed: bool = False) -> bool:
     """``write_vcf`` with the records formatted on ``device``: the same file, byte for byte.
 
     ``bgzf``: the file is bgzipped.  Each chunk's text is deflated into BGZF members of 0xff00 bytes and packed
@@ -132,7 +136,8 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
 
     ``info``: one INFO string per site row, as ``write_vcf(info=...)``: it takes the place of '.' in the line
     prefixes (host-built, of any width) and adds the four ##INFO header lines.  ``ids`` / ``ref`` / ``alt``: one
-    string per site row for the ID, REF and ALT columns, as ``write_vcf`` takes them ('.' without).
+    string per site row for the ID, REF and ALT columns, as ``write_vcf`` takes them ('.' without).  ``typed``: the
+    header also declares the TYPED flag, as ``write_vcf(typed=True)``; no record changes.
 
     ``index`` (needs ``bgzf``): also write the tabix index ``path + ".tbi"`` (dataset/tbi.py) without reading the
     file back.  The byte offset of every line in its chunk's text is known on the host; each chunk's member lengths
@@ -175,11 +180,11 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     if bgzf:
         from .dataset.bgzf import EOF_BLOCK, write_bgzf
         with open(path, "wb") as f:
-            write_bgzf(f, header_lines(samples, info is not None).encode(locale.getpreferredencoding(False)),
+            write_bgzf(f, header_lines(samples, info is not None, typed).encode(locale.getpreferredencoding(False)),
                        eof=not chunks)
     else:
         with open(path, "w") as f:
-            f.write(header_lines(samples, info is not None))
+            f.write(header_lines(samples, info is not None, typed))
     if not chunks:
         if index:
             tbi.build([], [], [], [], [], []).write(str(path) + ".tbi")
@@ -298,5 +303,5 @@ def write_vcf_device(path, chrom, pos, h1, h2, gt, samples, pos_flag=None, ref=N
     print("write_vcf_device: a value does not fit the fixed-width cell (NaN, infinite, negative or >= 9.9995); "
           "the host writer writes the file", flush=True)
     write_vcf(path, chrom, pos, _host(h1), _host(h2), _host(gt), samples, pos_flag=flag, ref=ref, alt=alt, bgzf=bgzf,
-              info=info, index=index, ids=ids)
+              info=info, index=index, ids=ids, typed=typed)
     return False
