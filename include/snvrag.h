@@ -625,7 +625,9 @@ int snvrag_colsum_bf16(int64_t M, int N, const void* x, float* out, void* ws, si
  * first; a parameter's f32 .grad can be passed directly), rows of dy / x ldy / ldx elements apart
  * (a column slice of a fused N: the q/k/v parts).  32x32x16 MFMAs on LDS-transposed tiles, M split into `splits` chunks (0: enough to fill
  * the chip, snvrag_dw_splits) whose 128 x 128 tiles are added with float atomics (the summation
- * order across chunks is not fixed).  N, K multiples of 128. */
+ * order across chunks is not fixed).  N, K multiples of 128.  M < 2^31, and a chunk's rows
+ * (M / splits rounded up to 32) x max(ldy, ldx) x 2 bytes must stay below 2 GiB (32-bit DMA offsets):
+ * a call beyond either is refused, in all four entry points. */
 int snvrag_dw_splits(int64_t M, int64_t N, int64_t K);
 int snvrag_linear_dw(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x, int64_t ldx,
                      float* dw, float* db, int splits, void* stream);

@@ -260,17 +260,31 @@ extern "C" int snvrag_dw_splits(int64_t M, int64_t N, int64_t K) {
 }
 
 // rows per chunk and the number of (non-empty) chunks: a function of (M, N, K, splits) alone
-static void dw_chunks(int64_t M, int64_t N, int64_t K, int splits, int& chunk, int& S) {
+static void dw_chunks(int64_t M, int64_t N, int64_t K, int splits, long& chunk, long& S) {
   if (splits <= 0) splits = snvrag_dw_splits(M, N, K);
-  chunk = (int)((((M + splits - 1) / splits) + DW_R - 1) / DW_R * DW_R);
-  S = (int)((M + chunk - 1) / chunk);
+  chunk = (((M + splits - 1) / splits) + DW_R - 1) / DW_R * DW_R;
+  S = (M + chunk - 1) / chunk;
+}
+
+// dw_chunks for a launch.  The kernel addresses a chunk's rows with 32-bit byte offsets from the
+// chunk's first row (voy / vox + st * sty / stx, and dma_rsrc clamps the resource to 2^31 - 1 bytes):
+// a chunk that spans 2 GiB or more would read zeros past the clamp, so it is refused here.
+static int dw_plan(int64_t M, int64_t N, int64_t K, int64_t ldy, int64_t ldx, int splits, int& chunk, int& S) {
+  long c, n;
+  dw_chunks(M, N, K, splits, c, n);
+  const long ld = std::max(ldy, ldx);
+  SNV_CHECK_ARG(ld < (1L << 30) && c * ld * 2 < (1L << 31),
+                "a chunk of rows spans 2 GiB or more (32-bit DMA offsets): use more splits");
+  chunk = (int)c;
+  S = (int)n;
+  return 0;
 }
 
 static int launch_dw(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x, int64_t ldx,
                      const DwOut& out, int splits, hipStream_t s) {
   if (M == 0) return 0;
   int chunk, S;
-  dw_chunks(M, N, K, splits, chunk, S);
+  if (int rc = dw_plan(M, N, K, ldy, ldx, splits, chunk, S)) return rc;
   evlog_begin(s);
   hipLaunchKernelGGL(dw_dma_kernel<false>, dim3((unsigned)((N / DW_T) * (K / DW_T) * S)), dim3(256), 0, s, (int)M,
                      (int)N, (int)K, (const bf16*)dy, (long)ldy, (const bf16*)x, (long)ldx, out, chunk,
@@ -283,6 +297,8 @@ static int launch_dw(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ld
 static int launch_dw_det(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x, int64_t ldx,
                          const DwOut& out, int splits, void* ws, size_t ws_bytes, hipStream_t s) {
   if (M == 0) return 0;
+  int chunk, S;
+  if (int rc = dw_plan(M, N, K, ldy, ldx, splits, chunk, S)) return rc;
   SNV_CHECK_ARG(ws && aligned(16, ws), "workspace: null or not 16-byte aligned");
   SNV_CHECK_ARG(ws_bytes >= snvrag_linear_dw_det_ws_bytes(M, N, K, splits),
                 "workspace smaller than snvrag_linear_dw_det_ws_bytes()");
@@ -291,8 +307,6 @@ static int launch_dw_det(int64_t M, int64_t N, int64_t K, const void* dy, int64_
     SNV_CHECK_ALIGN(16, "dw / db must be 16-byte aligned", out.w[i], out.b[i]);
     SNV_CHECK_ARG(!out.w[i] || (out.b[i] != nullptr) == has_b, "db: all parts or none");
   }
-  int chunk, S;
-  dw_chunks(M, N, K, splits, chunk, S);
   evlog_begin(s);
   hipLaunchKernelGGL(dw_dma_kernel<true>, dim3((unsigned)((N / DW_T) * (K / DW_T) * S)), dim3(256), 0, s, (int)M,
                      (int)N, (int)K, (const bf16*)dy, (long)ldy, (const bf16*)x, (long)ldx, out, chunk,
@@ -309,6 +323,7 @@ static int launch_dw_det(int64_t M, int64_t N, int64_t K, const void* dy, int64_
 static int dw_check(int64_t M, int64_t N, int64_t K, const void* dy, int64_t ldy, const void* x, int64_t ldx) {
   SNV_CHECK_PTRS(dy, x);
   SNV_CHECK_ARG(M >= 0 && N % DW_T == 0 && K % DW_T == 0 && N > 0 && K > 0, "N and K must be multiples of 128");
+  SNV_CHECK_M(M);                                    // (the kernel carries M as int)
   SNV_CHECK_ARG(ldy >= N && ldx >= K && ldy % 8 == 0 && ldx % 8 == 0, "leading dims: >= N / K, multiples of 8");
   SNV_CHECK_ALIGN(16, "operands must be 16-byte aligned", dy, x);
   return 0;
@@ -348,7 +363,7 @@ extern "C" int snvrag_linear_dw_parts(int64_t M, int64_t N, int64_t K, const voi
 
 extern "C" size_t snvrag_linear_dw_det_ws_bytes(int64_t M, int64_t N, int64_t K, int splits) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  int chunk, S;
+  long chunk, S;
   dw_chunks(M, N, K, splits, chunk, S);
   return (size_t)S * (size_t)(N * K + N) * sizeof(float);
 }

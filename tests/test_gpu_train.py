@@ -174,7 +174,8 @@ def test_hip_linear_backward(M, K_, N, multi):
                                             (4097, 384, 1536, 3), (24 * 2 * 1025, 384, 384, 0), (33, 256, 128, 64)])
 def test_linear_dw_kernel_vs_fp32(M, N, K_, splits):
     """dW = dy^T x and db = sum dy (csrc/dw.hip) against fp32 torch on the same bf16 values: ragged
-    M (not a multiple of the 32-row stage), more chunks than stages, the bench's 2BL rows."""
+    M (not a multiple of the 32-row stage), more chunks than stages, the bench's 2BL rows.
+    Kernel-level coverage (fp64 reference, per-element bounds, every ring, chunk and tile edge): test_gpu_linear_dw.py."""
     from src import kernels as K
     g = torch.Generator(device="cpu").manual_seed(M + N)
     dy = torch.randn(M, N, generator=g).to(DEV, torch.bfloat16)
